@@ -19,7 +19,9 @@ Without a launcher (`WORLD_SIZE` unset) `--gpus N` with N > 1 spawns the N ranks
 torch.distributed.run; it exits non-zero when fewer than N GPUs are visible -- it never prints an
 `n_gpus: 1` line for `--gpus 8`.  `--config 5` selects SURVEY.md sec. 8d config 5 (960x960, 25 channels,
 8 maps per GPU, all-gather of the predicted maps timed); `--maps file.npz` feeds a map sequence in the
-reference's on-disk format (nav/collect_maps.py:80-87) instead of synthetic maps.
+reference's on-disk format (nav/collect_maps.py:80-87) instead of synthetic maps.  `--dump-outputs DIR` writes what the
+last timed step computed to DIR as .npy (dump_outputs()), so that two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -96,6 +98,30 @@ def write_detail(detail: dict, path: str = "") -> str:
         except OSError:
             pass
     return written
+
+
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: all arrays together stay under this (the contract allows 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(out: torch.Tensor, directory: str, max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """--dump-outputs: what the caller of the timed path received from its last step, as DIR/probs.npy (float32).  The whole
+    [B,K,H,W] array when it fits in max_bytes; otherwise a fixed sample of it, the same for every run of the same shape:
+    positions drawn without replacement by a torch.Generator seeded with DUMP_SEED, sorted, their values as probs.npy (1-D)
+    and the flat positions themselves as probs_index.npy (float64, exact below 2**53).  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    n = out.numel()
+    if n * out.element_size() <= max_bytes:
+        arrays = {"probs": out.detach().float().cpu().numpy()}
+    else:
+        k = max_bytes // (4 + 8)
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:k].sort().values
+        arrays = {"probs": out.detach().reshape(-1)[idx.to(out.device)].float().cpu().numpy(),
+                  "probs_index": idx.numpy().astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def configs_summary(configs: dict) -> dict:
@@ -445,12 +471,18 @@ def main(argv=None, backend_factory=HipBackend):
                          "counters; 'auto' = measure at N=1 when rocprofv3 is installed, else the committed file")
     ap.add_argument("--op-table", default="", help="write the per-op timing table (JSON) here")
     ap.add_argument("--detail", default="", help="where the full measurement record goes (default: bench_detail.json next to this script)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the probabilities the last timed step returned (rank 0's shard) to "
+                         "DIR/probs.npy, float32; above 48 MiB a fixed seeded sample with its positions in DIR/probs_index.npy "
+                         "(dump_outputs()).  Inputs and weights are seeded: the same arguments give the same inputs on every run")
     ap.add_argument("--configs", default=os.environ.get("PEANUT_BENCH_CONFIGS", "4"),
                     help="the other BASELINE.json configurations measured after the headline (N = 1 only) and reported under "
                          "'configs' of bench_detail.json, each with its own roofline and cpu_baseline, flat numbers in the contract "
                          "line's configs_summary (tools/configs_bench.py); default 4 (the per-step pipeline, which also measures the "
                          "detector and the mapping stage), 'all' = 1,3,4,5,mapping, empty string to skip")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     preset = PRESETS[args.config]
     for k, v in preset.items():
         if getattr(args, k) is None:
@@ -481,9 +513,10 @@ def main(argv=None, backend_factory=HipBackend):
         x = synth_maps(B, cfg.in_channels, S, dev, seed0=rank * B)
     out = torch.empty((B, cfg.num_classes, S, S), dtype=torch.float32, device=dev)
 
-    def run_mode(precision, steps, warmup, op_table=""):
+    def run_mode(precision, steps, warmup, op_table="", dump=""):
         """W untimed warm-up steps, then exactly `steps` timed steps bracketed by barrier + synchronize;
-        returns (max-over-ranks seconds, roofline dict)."""
+        returns (max-over-ranks seconds, roofline dict).  `dump`: directory for dump_outputs() of the last timed step's result,
+        written before the probe pass below runs the model again."""
         model = backend.make_model(cfg, sd, precision)
         for _ in range(warmup):
             model.get_prediction_batch(x, apply_sigmoid=True, out=out)
@@ -496,6 +529,8 @@ def main(argv=None, backend_factory=HipBackend):
         backend.synchronize()
         pdist.barrier()
         elapsed = pdist.max_over_ranks(time.perf_counter() - t0, device=dev)
+        if dump and rank == 0:
+            dump_outputs(out, dump)
         roof = None
         if not args.no_probe:
             # second pass, after the timed steps: per-op HIP events on the launch stream (the probe serialises the two-stream
@@ -549,7 +584,7 @@ def main(argv=None, backend_factory=HipBackend):
         del model
         return elapsed, roof
 
-    elapsed, roof = run_mode(args.precision, args.steps, args.warmup, args.op_table)
+    elapsed, roof = run_mode(args.precision, args.steps, args.warmup, args.op_table, args.dump_outputs)
     modes = {}
     for extra in [m for m in args.also.split(",") if m and m != args.precision]:
         st = max(3, args.steps // 2)

@@ -17,8 +17,19 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _host_only_rank():
+    """First call of every worker process below: the ranks of this module run on the host.  On a box with a GPU, two
+    device probes would otherwise initialise the HIP runtime and open the GPU in each rank -- and eight ranks beside the
+    test runner are more processes than a shared GPU may have open at once: torch.cuda.is_available() in
+    pdist.init_process_group (which then binds the rank to a device) and torch._C._get_accelerator() in
+    torch.distributed.barrier (which picks the barrier's device; a gloo group takes the host anyway)."""
+    torch.cuda.is_available = lambda: False
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _worker(rank, world, port, q):
     try:
+        _host_only_rank()
         os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                           MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         r, lr, w = pdist.init_process_group(backend="gloo")
@@ -93,6 +104,7 @@ class _CountingAgent:
 
 def _worker8(rank, world, port, ep_dir, n_eps, q):
     try:
+        _host_only_rank()
         os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world),
                           MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         import sys
@@ -181,6 +193,7 @@ def _bench_worker(rank, world, port, q, break_gather):
     import io
     import json
     try:
+        _host_only_rank()
         os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         import bench
 
@@ -266,3 +279,64 @@ def test_bench_main_runs_its_multi_rank_control_flow_under_gloo(break_gather):
     assert roof["kernel"] == bench.DOMINANT_FAMILY_FP32 and roof["bound"] == "mfma"
     assert roof["traffic"] is not None and roof["traffic"] > 0 and roof["traffic_measured_by_this_run"] is False
     assert "NOT measured by this run" in detail["roofline"]["traffic_source"]
+
+
+class _CountingModel(_StubModel):
+    """Fills the output with the number of forwards run so far: the value tells which call produced it."""
+    calls = 0
+
+    def get_prediction_batch(self, x, apply_sigmoid=True, out=None):
+        _CountingModel.calls += 1
+        out.fill_(float(_CountingModel.calls))
+        return out
+
+
+def test_bench_steps_and_dump_outputs_on_one_rank(tmp_path, capsys):
+    """bench.py's main() with one rank and a stand-in model: --warmup W and --steps K run W + K forwards before the probe
+    pass, and --dump-outputs writes the result of the last TIMED step (call W + K), not of the probe pass that follows it."""
+    import json
+
+    import numpy as np
+
+    import bench
+
+    class CountingBackend:
+        name = "stub"
+        device = torch.device("cpu")
+
+        def synchronize(self):
+            pass
+
+        def make_model(self, cfg, sd, precision):
+            return _CountingModel(0)
+
+        def state_dict(self, cfg):
+            return {}
+
+    _CountingModel.calls = 0
+    dump = tmp_path / "dump"
+    bench.main(["--steps", "4", "--warmup", "2", "--batch", "2", "--size", "32", "--traffic", "none",
+                "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)], backend_factory=CountingBackend)
+    line = json.loads(capsys.readouterr().out.splitlines()[-1])
+    assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0
+    assert _CountingModel.calls == 2 + 4 + 4                  # warm-up, timed steps, probe pass
+    assert sorted(os.listdir(dump)) == ["probs.npy"]
+    probs = np.load(dump / "probs.npy")
+    assert probs.dtype == np.float32 and probs.shape == (2, 6, 32, 32) and (probs == 6.0).all()
+    with pytest.raises(SystemExit):
+        bench.main(["--steps", "0"], backend_factory=CountingBackend)
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path):
+    import numpy as np
+
+    import bench
+    out = torch.arange(6000, dtype=torch.float32).reshape(2, 3, 20, 50)
+    assert bench.dump_outputs(out, str(tmp_path / "a"), max_bytes=1200) == {"probs": [100], "probs_index": [100]}
+    bench.dump_outputs(out, str(tmp_path / "b"), max_bytes=1200)
+    pa, ia = np.load(tmp_path / "a" / "probs.npy"), np.load(tmp_path / "a" / "probs_index.npy")
+    assert pa.dtype == np.float32 and ia.dtype == np.float64
+    assert np.array_equal(pa, ia) and len(np.unique(ia)) == 100 and (np.diff(ia) > 0).all()     # values = their flat positions
+    assert np.array_equal(pa, np.load(tmp_path / "b" / "probs.npy"))
+    assert np.array_equal(ia, np.load(tmp_path / "b" / "probs_index.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 1200 + 2 * 128   # + .npy headers

@@ -159,3 +159,26 @@ def test_bench_default_command_form_prints_a_parseable_contract_line():
     assert os.path.exists(os.path.join(ROOT, line["detail"]))
     print(f"default bench form: {wall:.0f} s wall, line {len(json.dumps(line, separators=(',', ':')))} bytes, "
           f"{line['value']} maps/s, frac {line['roofline']['frac']}, traffic {line['roofline']['traffic']}")
+
+
+def test_bench_dump_outputs_are_the_timed_path_result(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path returned: the probabilities of the fp32 forward over the seeded
+    synthetic maps and seeded weights, reproduced here through the product path in this process."""
+    from types import SimpleNamespace
+
+    import numpy as np
+
+    import bench
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    dump = tmp_path / "dump"
+    line = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "2", "--size", "96", "--no-cpu-baseline", "--no-probe", "--also", "",
+                       "--traffic", "none", "--configs", "", "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(dump)) == ["probs.npy"]
+    got = np.load(dump / "probs.npy")
+    cfg = PredCfg()
+    model = PEANUT_Prediction_Model(SimpleNamespace(sem_gpu_id=0), state_dict=make_seeded_state_dict(cfg, seed=0), cfg=cfg, precision="fp32")
+    want = model.get_prediction_batch(bench.synth_maps(2, cfg.in_channels, 96, "cuda", seed0=0), apply_sigmoid=True).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want.shape == (2, cfg.num_classes, 96, 96)
+    assert np.abs(got - want).max() <= 1e-5

@@ -119,7 +119,10 @@ def test_oracle_reproduces_the_four_map_480_golden(golden_dir):
 
 def test_oracle_distance_to_fp64_reference(golden_dir):
     """The fp64 golden logits (the reference's model files run in float64, oracle/gen_golden.py) put a number on
-    'fp32-class': the oracle -- bit-identical to the reference's fp32 CPU path -- is within 1e-5 of them."""
+    'fp32-class': the oracle -- bit-identical to the reference's fp32 CPU path -- is within 1e-5 of them.  Bit identity
+    holds only where the CPU kernels sum in the fixture host's order (CPU model and thread count); there the oracle's
+    distance is also the recorded distance of the reference's fp32 path, to the bit.  Elsewhere the CPU kernels round
+    differently (test_oracle_reproduces_golden bounds that difference) and the 1e-5 bound is what carries over."""
     import numpy as np
     import torch
     from oracle import pspnet_ref
@@ -129,9 +132,11 @@ def test_oracle_distance_to_fp64_reference(golden_dir):
     cfg = PredCfg()
     sd = make_seeded_state_dict(cfg, 0)
     x = torch.from_numpy(z["odd_100/input"].astype(np.float32))
-    got = pspnet_ref.forward_batch(sd, x, cfg).numpy().astype(np.float64)
-    err = float(np.abs(got - z64["odd_100/logits64"]).max())
-    assert err <= 1e-5 and abs(err - float(z64["odd_100/fp32_cpu_reference_max_abs"])) <= 1e-9
+    got32 = pspnet_ref.forward_batch(sd, x, cfg).numpy()
+    err = float(np.abs(got32.astype(np.float64) - z64["odd_100/logits64"]).max())
+    assert err <= 1e-5
+    if np.array_equal(got32, z["odd_100/logits"]):
+        assert abs(err - float(z64["odd_100/fp32_cpu_reference_max_abs"])) <= 1e-9
 
 
 def _variant_cfg(z, name):

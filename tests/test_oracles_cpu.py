@@ -1,5 +1,6 @@
 """CPU checks of the stage-1 and stage-2 oracles (test infrastructure) against what pins them:
-* oracle/mapping_ref.py vs the golden sequences produced by the reference's own Semantic_Mapping (bit for bit);
+* oracle/mapping_ref.py vs the golden sequences produced by the reference's own Semantic_Mapping (bit for bit on the
+  fixture's host; the channel sums to 1e-6 relative on other CPUs);
 * oracle/rcnn_ref.py vs the known-answer vectors of detectron2's own published unit tests (v0.6:
   tests/layers/test_roi_align.py::test_forward_output, tests/modeling/test_anchor_generator.py::
   test_default_anchor_generator) -- the only numeric fixtures that exist for this stage, detectron2 itself being
@@ -29,7 +30,9 @@ def test_mapping_oracle_reproduces_reference_golden(golden_dir, fname, ncat):
                 fp, maps, _, pose = mapping_ref.forward(torch.from_numpy(obs), torch.from_numpy(rel[i]), maps, pose, cfg)
             assert np.array_equal(np.packbits(fp.numpy().astype(bool)), z[f"{name}/fp_map_bits"][i])
             assert np.array_equal(pose.numpy(), z[f"{name}/poses"][i])
-            assert np.array_equal(maps.double().sum((1, 2)).numpy(), z[f"{name}/channel_sums"][i])
+            # bit for bit on the fixture's host; another CPU's grid_sample kernels round the re-sampled map differently,
+            # a few float32 ulps per cell (about 1e-7 of a channel's sum)
+            np.testing.assert_allclose(maps.double().sum((1, 2)).numpy(), z[f"{name}/channel_sums"][i], rtol=1e-6, atol=0)
             assert np.array_equal((maps != 0).sum((1, 2)).numpy(), z[f"{name}/channel_nnz"][i])
 
 
