@@ -9,16 +9,20 @@ A "step" is one pass of the hot path (NCHW map batch resident in HBM -> NCHW pro
 over one batch of synthetic maps.  Rank 0 prints ONE JSON line -- the compact contract object
 (contract_line(): under 4 KB; the driver could not parse round 5's 23 KB line) -- and writes everything else it measured
 (per-family tables, extra precision modes, the other configurations with their stage tables) to bench_detail.json.
-`roofline` is measured live with HIP events recorded inside the timed region on the launch stream
-(peanut_pred_probe_*); `roofline.traffic` comes from a rocprofv3 PMC pass over this very command that
-bench.py runs on itself as a child (separate FETCH_SIZE / WRITE_SIZE passes, --kernel-trace only);
-`cpu_baseline` times the oracle restatement of the reference's fp32 PyTorch path on this box's host
-cores (rank 0, N=1 only, bounded sample: BASELINE.md sec. 4 -- 2 warm-ups, best of 5, B=1 and B=4).
+
+A plain run measures the headline figure and nothing else: it sets up, runs the W warm-up and K timed steps, writes
+--dump-outputs and prints the line, whose `roofline` and `cpu_baseline` are then null.  `--full` adds everything else:
+`roofline`, measured with HIP events on the launch stream (peanut_pred_probe_*) over a second pass right after the timed
+steps; `roofline.traffic`, from rocprofv3 PMC passes over a short plain run of this command that bench.py starts as a
+child (separate FETCH_SIZE / WRITE_SIZE passes, --kernel-trace only); `cpu_baseline`, the oracle restatement of the
+reference's fp32 PyTorch path timed on the host cores (rank 0, N=1 only, bounded sample: BASELINE.md sec. 4 -- 2 warm-ups,
+best of 5, B=1 and B=4); the --also precision modes; the --configs configurations; the timed all-gather of the predicted
+maps (N > 1 and --config 5).
 
 Without a launcher (`WORLD_SIZE` unset) `--gpus N` with N > 1 spawns the N ranks itself through
 torch.distributed.run; it exits non-zero when fewer than N GPUs are visible -- it never prints an
 `n_gpus: 1` line for `--gpus 8`.  `--config 5` selects SURVEY.md sec. 8d config 5 (960x960, 25 channels,
-8 maps per GPU, all-gather of the predicted maps timed); `--maps file.npz` feeds a map sequence in the
+8 maps per GPU, all-gather of the predicted maps timed with --full); `--maps file.npz` feeds a map sequence in the
 reference's on-disk format (nav/collect_maps.py:80-87) instead of synthetic maps.  `--dump-outputs DIR` writes what the
 last timed step computed to DIR as .npy (dump_outputs()), so that two builds run with the same arguments can be compared
 output for output.
@@ -452,7 +456,7 @@ def main(argv=None, backend_factory=HipBackend):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=sorted(PRESETS),
                     help="SURVEY.md sec. 8d configuration: 2 = headline (480x480, 14 ch, 32 maps/GPU), "
-                         "5 = 960x960, 25 ch, 8 maps/GPU + all-gather of the predicted maps")
+                         "5 = 960x960, 25 ch, 8 maps/GPU + all-gather of the predicted maps (timed with --full)")
     ap.add_argument("--batch", type=int, default=None, help="maps per GPU per step (overrides the preset)")
     ap.add_argument("--size", type=int, default=None)
     ap.add_argument("--channels", type=int, default=None, help="4 + N_cat input channels")
@@ -460,29 +464,46 @@ def main(argv=None, backend_factory=HipBackend):
                                                "collect_maps.py format) used as input instead of synthetic maps")
     ap.add_argument("--precision", default=os.environ.get("PEANUT_PRECISION", "fp32"),
                     choices=sorted(PEAK_TFLOPS), help="conv arithmetic (include/peanut_hip.h PEANUT_PREC_*)")
-    ap.add_argument("--also", default=os.environ.get("PEANUT_BENCH_ALSO"),
-                    help="comma list of extra precision modes measured after the main run and reported under "
-                         "'modes' of bench_detail.json ('all' = bf16x6,fp16x3,bf16x3); default: none -- the driver form measures "
-                         "the fp32 headline only (tools/final_measure.sh asks for all of them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-op HIP-event probe")
-    ap.add_argument("--traffic", default="auto", choices=["auto", "measure", "file", "none"],
-                    help="roofline.traffic: 'measure' profiles a short child run of this command with rocprofv3 PMC "
-                         "counters; 'auto' = measure at N=1 when rocprofv3 is installed, else the committed file")
-    ap.add_argument("--op-table", default="", help="write the per-op timing table (JSON) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the per-op probe and roofline, the PMC traffic "
+                         "passes, the CPU baseline, the --also modes, the --configs configurations and the all-gather of the "
+                         "predicted maps.  Without it a run only sets up, warms up, times the steps, writes --dump-outputs and "
+                         "prints the line (roofline and cpu_baseline null)")
+    ap.add_argument("--also", default=None,
+                    help="with --full: comma list of extra precision modes measured after the main run and reported under "
+                         "'modes' of bench_detail.json ('all' = bf16x6,fp16x3,bf16x3); default: $PEANUT_BENCH_ALSO, else none "
+                         "(tools/final_measure.sh asks for all of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="with --full: skip the per-op HIP-event probe (and so the roofline)")
+    ap.add_argument("--traffic", default=None, choices=["auto", "measure", "file", "none"],
+                    help="with --full: roofline.traffic: 'measure' profiles a short child run of this command with rocprofv3 PMC "
+                         "counters; 'auto' (the default) = measure at N=1 when rocprofv3 is installed, else the committed file")
+    ap.add_argument("--op-table", default="", help="with --full: write the per-op timing table (JSON) here")
     ap.add_argument("--detail", default="", help="where the full measurement record goes (default: bench_detail.json next to this script)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write the probabilities the last timed step returned (rank 0's shard) to "
                          "DIR/probs.npy, float32; above 48 MiB a fixed seeded sample with its positions in DIR/probs_index.npy "
                          "(dump_outputs()).  Inputs and weights are seeded: the same arguments give the same inputs on every run")
-    ap.add_argument("--configs", default=os.environ.get("PEANUT_BENCH_CONFIGS", "4"),
-                    help="the other BASELINE.json configurations measured after the headline (N = 1 only) and reported under "
-                         "'configs' of bench_detail.json, each with its own roofline and cpu_baseline, flat numbers in the contract "
-                         "line's configs_summary (tools/configs_bench.py); default 4 (the per-step pipeline, which also measures the "
-                         "detector and the mapping stage), 'all' = 1,3,4,5,mapping, empty string to skip")
+    ap.add_argument("--configs", default=None,
+                    help="with --full: the other BASELINE.json configurations measured after the headline (N = 1 only) and reported "
+                         "under 'configs' of bench_detail.json, each with its own roofline and cpu_baseline, flat numbers in the "
+                         "contract line's configs_summary (tools/configs_bench.py); default $PEANUT_BENCH_CONFIGS, else 4 (the "
+                         "per-step pipeline, which also measures the detector and the mapping stage), 'all' = 1,3,4,5,mapping, "
+                         "empty string to skip")
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.full:
+        args.also = os.environ.get("PEANUT_BENCH_ALSO", "") if args.also is None else args.also
+        args.configs = os.environ.get("PEANUT_BENCH_CONFIGS", "4") if args.configs is None else args.configs
+        args.traffic = args.traffic or "auto"
+    else:
+        asked = [f"{flag} {v}" for flag, v in (("--also", args.also), ("--configs", args.configs), ("--op-table", args.op_table),
+                                               ("--traffic", args.traffic)) if v and v != "none"]
+        if asked:
+            ap.error(f"{', '.join(asked)}: measures beyond the headline figure, which only a --full run does")
+        args.also, args.configs, args.traffic = "", "", "none"
+        args.no_cpu_baseline = args.no_probe = True
     preset = PRESETS[args.config]
     for k, v in preset.items():
         if getattr(args, k) is None:
@@ -496,8 +517,6 @@ def main(argv=None, backend_factory=HipBackend):
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     backend = backend_factory()
     dev = backend.device
-    if args.also is None:
-        args.also = ""
     if args.also == "all":
         args.also = "bf16x6,fp16x3,bf16x3"
     if args.configs == "all":
@@ -592,9 +611,8 @@ def main(argv=None, backend_factory=HipBackend):
         if rank == 0 and world == 1 and e_roof is not None and args.traffic in ("auto", "measure") and not args.maps:
             # the same three PMC child passes as for the headline: HBM traffic, matrix-pipe busy share and effective clock of
             # this mode's dominant kernel
-            child = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-probe", "--also", "", "--traffic", "none", "--configs", "",
-                     "--config", str(args.config), "--batch", str(B), "--size", str(S), "--channels", str(cfg.in_channels),
-                     "--precision", extra]
+            child = ["--steps", "2", "--warmup", "1", "--config", str(args.config), "--batch", str(B), "--size", str(S),
+                     "--channels", str(cfg.in_channels), "--precision", extra]
             got = measure_hbm_traffic(e_roof["kernel"], child)
             if got:
                 e_roof.update(got)
@@ -605,7 +623,7 @@ def main(argv=None, backend_factory=HipBackend):
     # logging-only collective: collate the predicted maps of the last step (outside the timed steps; timed on its own)
     gather_ms = None
     gather_failed = False
-    if world > 1 or args.config == 5:
+    if args.full and (world > 1 or args.config == 5):
         gather = pdist.allgather_maps                  # peanut_allgather_maps (the library's RCCL entry point)
         # one rank (--config 5 at N = 1): peanut_amd.dist.allgather_maps returns its input untouched -- nothing goes through RCCL
         gather_path = "peanut_allgather_maps (RCCL)" if world > 1 else "identity (1 rank: RCCL not used)"
@@ -654,9 +672,9 @@ def main(argv=None, backend_factory=HipBackend):
     if rank == 0 and roof is not None and args.traffic != "none":
         measured = None
         if world == 1 and args.traffic in ("auto", "measure"):
-            child = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-probe", "--also", "", "--traffic", "none", "--configs", "",
-                     "--config", str(args.config), "--batch", str(B), "--size", str(S), "--channels", str(cfg.in_channels),
-                     "--precision", args.precision] + (["--maps", os.path.abspath(args.maps)] if args.maps else [])
+            child = ["--steps", "2", "--warmup", "1", "--config", str(args.config), "--batch", str(B), "--size", str(S),
+                     "--channels", str(cfg.in_channels), "--precision", args.precision] + \
+                    (["--maps", os.path.abspath(args.maps)] if args.maps else [])
             measured = measure_hbm_traffic(roof["kernel"], child)
         roof["traffic_measured_by_this_run"] = bool(measured is not None and measured.get("traffic") is not None)
         if roof["traffic_measured_by_this_run"]:

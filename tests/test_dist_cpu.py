@@ -224,8 +224,8 @@ def _bench_worker(rank, world, port, q, break_gather):
             try:
                 import tempfile
                 detail = os.path.join(tempfile.gettempdir(), f"peanut_bench_detail_{port}.json")
-                bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "32", "--detail", detail],
-                           backend_factory=StubBackend)
+                bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "32", "--detail", detail,
+                            "--full"], backend_factory=StubBackend)
             except SystemExit as e:
                 code = e.code if isinstance(e.code, int) else 1
         out_lines = buf.getvalue().splitlines()
@@ -245,7 +245,7 @@ def _bench_worker(rank, world, port, q, break_gather):
 
 @pytest.mark.parametrize("break_gather", [False, True], ids=["gather_ok", "gather_falls_back"])
 def test_bench_main_runs_its_multi_rank_control_flow_under_gloo(break_gather):
-    """bench.py's main() with WORLD_SIZE = 2 on gloo and a stand-in model: both ranks pass the barriers, the step time is the
+    """bench.py's main() --full with WORLD_SIZE = 2 on gloo and a stand-in model: both ranks pass the barriers, the step time is the
     max over ranks, ONLY rank 0 prints the JSON line, the line carries n_gpus = 2, weak scaling, the whole-job value, the
     all-gather time, rccl_ranks_seen and a roofline whose traffic came from the committed file (no PMC child pass at
     N > 1), the extra precision modes are skipped -- and when the library's all-gather entry fails, the run still prints
@@ -291,8 +291,22 @@ class _CountingModel(_StubModel):
         return out
 
 
+class _CountingBackend:
+    name = "stub"
+    device = torch.device("cpu")
+
+    def synchronize(self):
+        pass
+
+    def make_model(self, cfg, sd, precision):
+        return _CountingModel(0)
+
+    def state_dict(self, cfg):
+        return {}
+
+
 def test_bench_steps_and_dump_outputs_on_one_rank(tmp_path, capsys):
-    """bench.py's main() with one rank and a stand-in model: --warmup W and --steps K run W + K forwards before the probe
+    """bench.py's main() --full with one rank and a stand-in model: --warmup W and --steps K run W + K forwards before the probe
     pass, and --dump-outputs writes the result of the last TIMED step (call W + K), not of the probe pass that follows it."""
     import json
 
@@ -300,23 +314,10 @@ def test_bench_steps_and_dump_outputs_on_one_rank(tmp_path, capsys):
 
     import bench
 
-    class CountingBackend:
-        name = "stub"
-        device = torch.device("cpu")
-
-        def synchronize(self):
-            pass
-
-        def make_model(self, cfg, sd, precision):
-            return _CountingModel(0)
-
-        def state_dict(self, cfg):
-            return {}
-
     _CountingModel.calls = 0
     dump = tmp_path / "dump"
-    bench.main(["--steps", "4", "--warmup", "2", "--batch", "2", "--size", "32", "--traffic", "none",
-                "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)], backend_factory=CountingBackend)
+    bench.main(["--steps", "4", "--warmup", "2", "--batch", "2", "--size", "32", "--traffic", "none", "--full",
+                "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)], backend_factory=_CountingBackend)
     line = json.loads(capsys.readouterr().out.splitlines()[-1])
     assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0
     assert _CountingModel.calls == 2 + 4 + 4                  # warm-up, timed steps, probe pass
@@ -324,7 +325,35 @@ def test_bench_steps_and_dump_outputs_on_one_rank(tmp_path, capsys):
     probs = np.load(dump / "probs.npy")
     assert probs.dtype == np.float32 and probs.shape == (2, 6, 32, 32) and (probs == 6.0).all()
     with pytest.raises(SystemExit):
-        bench.main(["--steps", "0"], backend_factory=CountingBackend)
+        bench.main(["--steps", "0"], backend_factory=_CountingBackend)
+
+
+def test_plain_bench_run_does_only_the_headline_steps(tmp_path, capsys, monkeypatch):
+    """bench.py's main() without --full: W + K forwards and nothing after them -- no probe pass, no extra precision mode even
+    when $PEANUT_BENCH_ALSO names one, no all-gather at --config 5 -- the dump of the last timed step, and a line whose
+    roofline and cpu_baseline are null.  Options that measure beyond the headline figure are refused without --full."""
+    import json
+
+    import numpy as np
+
+    import bench
+    monkeypatch.setenv("PEANUT_BENCH_ALSO", "bf16x6")
+    monkeypatch.setenv("PEANUT_BENCH_CONFIGS", "4")
+    for config in ("2", "5"):
+        _CountingModel.calls = 0
+        dump = tmp_path / f"dump{config}"
+        bench.main(["--config", config, "--steps", "4", "--warmup", "2", "--batch", "2", "--size", "32",
+                    "--detail", str(tmp_path / "detail.json"), "--dump-outputs", str(dump)], backend_factory=_CountingBackend)
+        line = json.loads(capsys.readouterr().out.splitlines()[-1])
+        assert _CountingModel.calls == 2 + 4                   # warm-up, timed steps
+        assert line["steps"] == 4 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "maps/s"
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        assert not {"modes_summary", "configs_summary", "allgather_maps_ms", "hbm_bound_frac_of_8tbs"} & set(line)
+        assert sorted(os.listdir(dump)) == ["probs.npy"] and (np.load(dump / "probs.npy") == 6.0).all()
+    for extra in (["--also", "bf16x6"], ["--configs", "4"], ["--traffic", "measure"], ["--op-table", str(tmp_path / "ops.json")]):
+        with pytest.raises(SystemExit) as e:
+            bench.main(["--steps", "1"] + extra, backend_factory=_CountingBackend)
+        assert e.value.code == 2, extra
 
 
 def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path):

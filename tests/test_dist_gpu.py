@@ -64,11 +64,11 @@ def test_single_rank_communicator_and_rccl_binding():
 
 
 def test_bench_spawns_its_own_ranks_or_refuses():
-    """`python bench.py --gpus N` without a launcher must run N ranks (n_gpus == N in the JSON line) or exit
-    non-zero -- never report a smaller job under that flag."""
+    """`python bench.py --gpus N --full` without a launcher must run N ranks (n_gpus == N in the JSON line, with the all-gather
+    of the predicted maps) or exit non-zero -- never report a smaller job under that flag."""
     have = torch.cuda.device_count()
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "96",
-            "--no-cpu-baseline", "--also", "", "--traffic", "none"]
+            "--no-cpu-baseline", "--also", "", "--traffic", "none", "--full"]
     r = subprocess.run(base + ["--gpus", str(have + 1)], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
     assert r.returncode != 0 and '"n_gpus"' not in r.stdout
     n = min(2, have)
@@ -79,7 +79,7 @@ def test_bench_spawns_its_own_ranks_or_refuses():
         assert line["n_gpus"] == n and line["config"]["global_batch"] == 2 * n and "allgather_maps_ms" in line
     # config-5 preset (per-GPU shard shrunk to keep the test short): the all-gather is timed and reported
     r = subprocess.run(base[:2] + ["--config", "5", "--steps", "1", "--warmup", "1", "--batch", "1", "--size", "192", "--no-cpu-baseline",
-                                   "--also", "", "--traffic", "none"], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                                   "--also", "", "--traffic", "none", "--full"], env=_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -99,7 +99,7 @@ def _run_bench(args, timeout=900):
     return json.loads(lines[0])
 
 
-def _check_contract(line, steps, warmup, batch):
+def _check_contract(line, steps, warmup, batch, full=True):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "detail"):
         assert k in line, k
@@ -107,6 +107,9 @@ def _check_contract(line, steps, warmup, batch):
     assert line["higher_is_better"] is True and line["scaling"] == "weak" and line["vs_baseline"] is None
     assert line["dtype"] == "f32" and line["data"] == "synthetic" and "workload" in line["config"] and "model" not in line["config"]
     assert abs(line["value"] - batch * steps / (line["ms_per_step"] * steps * 1e-3)) <= 0.01 * line["value"]
+    if not full:                 # a plain run measures the headline figure only
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        return
     roof = line["roofline"]
     for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "launches_per_step",
               "avg_launch_ms"):
@@ -120,12 +123,12 @@ def _check_contract(line, steps, warmup, batch):
 
 @pytest.mark.slow
 def test_bench_line_carries_the_contract_fields(tmp_path):
-    """The ONE JSON line of bench.py (small shape, short run): the driver's fields, the roofline and cpu_baseline objects reduced
+    """The ONE JSON line of bench.py --full (small shape, short run): the driver's fields, the roofline and cpu_baseline objects reduced
     to their numbers, flat summaries of the requested modes; the per-family tables and the modes' own rooflines are in the detail
     file the line names."""
     detail_path = str(tmp_path / "detail.json")
     line = _run_bench(["--steps", "3", "--warmup", "1", "--batch", "2", "--size", "96", "--also", "bf16x6,fp16x3", "--traffic", "none",
-                       "--detail", detail_path])
+                       "--detail", detail_path, "--full"])
     _check_contract(line, 3, 1, 2)
     assert set(line["modes_summary"]) == {"bf16x6", "fp16x3"} and all(m["value"] > 0 for m in line["modes_summary"].values())
     assert {"nchw_to_nhwc", "maxpool", "ppm_pool", "upsample_logits"} <= set(line["hbm_bound_frac_of_8tbs"])
@@ -141,12 +144,12 @@ def test_bench_line_carries_the_contract_fields(tmp_path):
 
 @pytest.mark.slow
 def test_bench_default_command_form_prints_a_parseable_contract_line():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the driver's own command form, every default in force (headline at
-    480 x 480 x 14, batch 32, PMC traffic passes, CPU baseline, config 4 with the detector and the mapping stage): the last
-    stdout line is the contract object, strict JSON under 4 KB, with a measured roofline, a cpu_baseline and the flat
-    configs_summary (round 5's line was 23 KB and the driver recorded parsed = null)."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's own command form plus --full, every other default
+    in force (headline at 480 x 480 x 14, batch 32, PMC traffic passes, CPU baseline, config 4 with the detector and the
+    mapping stage): the last stdout line is the contract object, strict JSON under 4 KB, with a measured roofline, a
+    cpu_baseline and the flat configs_summary (round 5's line was 23 KB and the driver recorded parsed = null)."""
     t0 = __import__("time").perf_counter()
-    line = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=1500)
+    line = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], timeout=1500)
     wall = __import__("time").perf_counter() - t0
     _check_contract(line, 20, 5, 32)
     assert line["config"]["survey_config"] == 2 and line["config"]["global_batch"] == 32
@@ -157,8 +160,24 @@ def test_bench_default_command_form_prints_a_parseable_contract_line():
     for k in ("config4_steps_s", "detector_b1_ms_per_frame", "pred720_b1_ms_per_map", "mapping_steps_s", "config3_images_s"):
         assert cs.get(k) and cs[k] > 0, (k, cs)
     assert os.path.exists(os.path.join(ROOT, line["detail"]))
-    print(f"default bench form: {wall:.0f} s wall, line {len(json.dumps(line, separators=(',', ':')))} bytes, "
+    print(f"full bench form: {wall:.0f} s wall, line {len(json.dumps(line, separators=(',', ':')))} bytes, "
           f"{line['value']} maps/s, frac {line['roofline']['frac']}, traffic {line['roofline']['traffic']}")
+
+
+@pytest.mark.slow
+def test_bench_plain_command_form_spends_at_most_30_s_outside_its_steps():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` -- the driver's own command form, which measures the headline figure only:
+    the contract line with null roofline and cpu_baseline, and at most 30 s from start to exit beyond the 25 steps themselves
+    (ms_per_step x (steps + warmup)), set-up and the first step's code loading included."""
+    t0 = __import__("time").perf_counter()
+    line = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=600)
+    wall = __import__("time").perf_counter() - t0
+    _check_contract(line, 20, 5, 32, full=False)
+    assert line["config"]["survey_config"] == 2 and line["config"]["global_batch"] == 32
+    assert not {"modes_summary", "configs_summary", "allgather_maps_ms"} & set(line)
+    outside = wall - 25 * line["ms_per_step"] * 1e-3
+    print(f"plain bench form: {wall:.1f} s wall, {outside:.1f} s outside the steps, {line['value']} maps/s")
+    assert outside <= 30.0, (wall, line["ms_per_step"])
 
 
 def test_bench_dump_outputs_are_the_timed_path_result(tmp_path):
