@@ -502,7 +502,11 @@ int peanut_goal_select_begin(peanut_goal_t* g, const float* full_obstacle, const
  * (clip(loc + lmb[0/2], 0, full - 1)), weights exp(-dd / (dist_weight_temperature / map_resolution)) over the local
  * window lmb = {gx1, gx2, gy1, gy2} with the "sum < 10: keep the last weights" rule, value = target_pred * weights
  * (temperature -1: target_pred alone; 0: frontier mode, exp(-dd'/100) with dd' = inf below 60) and its
- * first-occurrence argmax.  target_pred device fp32 [gx2-gx1, gy2-gy1].  Outputs (host): goal_rc_out = the argmax
+ * argmax.  As in the reference, dd is the field after `dd[dd == max(dd)] = inf` (:393): when every cell of the map
+ * is reached, the farthest ones weigh 0.  The argmax has np.argmax's semantics (first occurrence; the first NaN wins;
+ * always a cell of the window); the sum of the weights is reduced in a fixed order (the same bits on every run).
+ * Frontier mode neither uses nor replaces the last weights, and a window of another size forgets them.
+ * target_pred device fp32 [gx2-gx1, gy2-gy1].  Outputs (host): goal_rc_out = the argmax
  * cell in local-map coordinates (`np.unravel_index(value.argmax(), value.shape)`); stats_out (optional) =
  * {value max, sum of the fresh weights, 1 if the last weights were kept, relaxation rounds}; dist_out (optional,
  * device double [H,W], +inf = masked / unreachable) and value_out (optional, device double [w,h]) for tests.

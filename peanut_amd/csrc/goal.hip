@@ -37,8 +37,10 @@
 // goal cell to equality.
 //
 // The rest of update_global_goal is fused around it: obstacle dilation by the collision disk + collision / visited
-// overrides -> traversible map (:382-386), exp(-d / temperature) weights with the "stuck: keep the last weights"
-// rule (:395-399), value = target_pred * weights and its first-occurrence argmax (:401-413).
+// overrides -> traversible map (:382-386), the fill (:392-393: the cells equal to the field's maximum become +inf -- the
+// unreached ones, or the farthest reached ones when every cell was reached), exp(-d / temperature) weights with the "stuck:
+// keep the last weights" rule (:395-399; their sum is reduced in a fixed order, so the rule decides the same on every run),
+// value = target_pred * weights and its argmax with np.argmax's semantics (first occurrence; the first NaN wins) (:401-413).
 //
 // The field needs the map, not the prediction: peanut_goal_select_begin puts the traversible map, the initialisation and the first
 // batch of relaxation rounds on a stream of the handle at once; the forward the caller enqueues next (Agent_State.update_state:
@@ -546,14 +548,29 @@ __global__ __launch_bounds__(256) void fmm_fill_kernel(const double* __restrict_
   out[i] = v < INFINITY ? v : __longlong_as_double((long long)*max_bits) + 1.0;
 }
 
+// max over ALL cells, +inf included (for `dd[dd == np.max(dd)] = np.inf` after the fill, :392-393): +inf when some cell is masked or
+// unreached -- the rule then turns exactly those (filled with max + 1) into +inf, which they already are -- else the farthest
+// reached distance, whose cells the rule turns into +inf too.  Bits of a non-negative double order like an integer.
+__global__ __launch_bounds__(256) void goal_field_max_kernel(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
+  double m = 0.0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = fmax(m, dist[i]);
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) atomicMax(max_bits, (unsigned long long)__double_as_longlong(m));
+}
+
 // ---- weights over the local window: exp(-dd / temperature) (:395-396), their sum (:398) ----
+// One partial sum per workgroup (fixed order inside it); goal_sum_kernel adds the partials in index order, so the sum -- and the
+// "sum < 10: keep the last weights" decision -- is the same bits on every run.
 __global__ __launch_bounds__(256) void goal_weight_kernel(const double* __restrict__ dist, int W, int gx1, int gy1, int lw, int lh,
-                                                          double temperature, int frontier, double* __restrict__ wt, double* __restrict__ sum) {
+                                                          double temperature, int frontier, const unsigned long long* __restrict__ field_max,
+                                                          double* __restrict__ wt, double* __restrict__ part_out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
+  const double dmax = __longlong_as_double((long long)*field_max);
   double w = 0.0;
   if (i < lw * lh) {
     const int r = i / lh, c = i - r * lh;
     double dd = dist[(size_t)(gx1 + r) * W + (gy1 + c)];
+    if (dd == dmax) dd = INFINITY;      // (:393; a no-op unless every cell of the map was reached)
     if (frontier) {            // dist_weight_temperature == 0: frontier-based exploration (:404-406)
       if (dd < 60.0) dd = INFINITY;
       w = exp(-dd / 100.0);
@@ -566,12 +583,29 @@ __global__ __launch_bounds__(256) void goal_weight_kernel(const double* __restri
   __shared__ double part[4];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = w;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(sum, (part[0] + part[1]) + (part[2] + part[3]));
+  if (threadIdx.x == 0) part_out[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+// the partials of goal_weight_kernel in a fixed order: lane t adds t, t + 256, ... in turn, then a fixed tree
+__global__ __launch_bounds__(256) void goal_sum_kernel(const double* __restrict__ part, int nparts, double* __restrict__ sum) {
+  double w = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) w += part[i];
+  for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o);
+  __shared__ double p[4];
+  if ((threadIdx.x & 63) == 0) p[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) *sum = (p[0] + p[1]) + (p[2] + p[3]);
 }
 
-// value = target_pred * dd_wt (or one of them alone) and its first-occurrence argmax (:401-413); two stages
+// value = target_pred * dd_wt (or one of them alone) and its first-occurrence argmax (:401-413); two stages.
+// np.argmax semantics: NaN ranks above every number (the first NaN wins), ties go to the smaller index.  The neutral element
+// {-inf, INT_MAX} loses to every real candidate (-inf included, by index), so the result is always an index of the window.
 struct ArgMax { double v; int i; };
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) { return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a; }
+__device__ __forceinline__ bool beats(ArgMax b, ArgMax a) {
+  const bool bn = b.v != b.v, an = a.v != a.v;
+  if (bn != an) return bn;
+  return (bn || b.v == a.v) ? b.i < a.i : b.v > a.v;
+}
+__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) { return beats(b, a) ? b : a; }
 __global__ __launch_bounds__(256) void goal_argmax_kernel(const float* __restrict__ target_pred, const double* __restrict__ wt_new,
                                                           const double* __restrict__ wt_last, const double* __restrict__ sum, int have_last,
                                                           int mode, int n, double* __restrict__ value_out, ArgMax* __restrict__ partial) {
@@ -583,7 +617,7 @@ __global__ __launch_bounds__(256) void goal_argmax_kernel(const float* __restric
     const double tp = target_pred ? (double)target_pred[i] : 1.0;
     const double v = mode == 1 ? tp : (mode == 2 ? wt[i] : tp * wt[i]);
     if (value_out) value_out[i] = v;
-    if (v > best.v) { best.v = v; best.i = i; }       // ascending i per lane: ties keep the first
+    best = better(best, ArgMax{v, i});                // ascending i per lane: ties keep the first
   }
   for (int o = 32; o > 0; o >>= 1) {
     ArgMax other{__shfl_xor(best.v, o), __shfl_xor(best.i, o)};
@@ -620,7 +654,7 @@ using namespace peanut;
 struct peanut_goal {
   peanut::Options opts = peanut::default_options();   // tuning options of this handle (options.h): snapshot at creation
   int H = 0, W = 0, rad = 0, tiles_x = 0, tiles_y = 0;
-  DevBuf trav, state, dist, order, active, counters, maxbits, wt_new, wt_last, sum, partial, out_idx, out_val, value;
+  DevBuf trav, state, dist, order, active, counters, maxbits, wt_new, wt_last, wt_part, sum, partial, out_idx, out_val, value;
   bool have_last = false;
   int last_lw = 0, last_lh = 0;
   int last_rounds = 0, last_passes = 0;
@@ -776,8 +810,8 @@ int peanut_goal_create(peanut_goal_t** out, int full_h, int full_w, int col_rad)
   int rc;
   if ((rc = g->trav.ensure(n)) || (rc = g->state.ensure(n)) || (rc = g->dist.ensure(n * sizeof(double))) ||
       (rc = g->order.ensure(n * sizeof(double))) || (rc = g->active.ensure(4 * (size_t)g->tiles_x * g->tiles_y)) || (rc = g->counters.ensure(MAX_ROUNDS_PER_CHECK * sizeof(unsigned int))) ||
-      (rc = g->maxbits.ensure(sizeof(unsigned long long))) || (rc = g->wt_new.ensure(n * sizeof(double))) ||
-      (rc = g->wt_last.ensure(n * sizeof(double))) || (rc = g->value.ensure(n * sizeof(double))) || (rc = g->sum.ensure(sizeof(double))) ||
+      (rc = g->maxbits.ensure(2 * sizeof(unsigned long long))) || (rc = g->wt_new.ensure(n * sizeof(double))) ||
+      (rc = g->wt_last.ensure(n * sizeof(double))) || (rc = g->wt_part.ensure((n + 255) / 256 * sizeof(double))) || (rc = g->value.ensure(n * sizeof(double))) || (rc = g->sum.ensure(sizeof(double))) ||
       (rc = g->partial.ensure(1024 * sizeof(ArgMax))) || (rc = g->out_idx.ensure(2 * sizeof(int))) || (rc = g->out_val.ensure(2 * sizeof(double))))
     return rc;
   *out = g.release();
@@ -923,9 +957,13 @@ int peanut_goal_select(peanut_goal_t* g, const float* full_obstacle, const uint8
   if (g->have_last && (g->last_lw != lw || g->last_lh != lh)) g->have_last = false;
   const int n = lw * lh;
   const double temperature = dist_weight_temperature / (double)map_resolution;      // (:395)
-  PEANUT_HIP_CHECK(hipMemsetAsync(g->sum.p, 0, sizeof(double), s));
-  hipLaunchKernelGGL(goal_weight_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const double*)g->dist.p, g->W, gx1, gy1, lw, lh,
-                     temperature, mode == 2 ? 1 : 0, (double*)g->wt_new.p, (double*)g->sum.p);
+  unsigned long long* field_max = (unsigned long long*)g->maxbits.p + 1;      // (slot 0: peanut_fmm_distance's fill)
+  PEANUT_HIP_CHECK(hipMemsetAsync(field_max, 0, sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(goal_field_max_kernel, dim3(256), dim3(256), 0, s, (const double*)g->dist.p, g->H * g->W, field_max);
+  const int nwt = (n + 255) / 256;
+  hipLaunchKernelGGL(goal_weight_kernel, dim3(nwt), dim3(256), 0, s, (const double*)g->dist.p, g->W, gx1, gy1, lw, lh,
+                     temperature, mode == 2 ? 1 : 0, (const unsigned long long*)field_max, (double*)g->wt_new.p, (double*)g->wt_part.p);
+  hipLaunchKernelGGL(goal_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)g->wt_part.p, nwt, (double*)g->sum.p);
   const int nparts = std::min(1024, (n + 255) / 256);
   hipLaunchKernelGGL(goal_argmax_kernel, dim3(nparts), dim3(256), 0, s, target_pred, (const double*)g->wt_new.p, (const double*)g->wt_last.p,
                      (const double*)g->sum.p, g->have_last ? 1 : 0, mode, n, value_out ? value_out : (double*)g->value.p, (ArgMax*)g->partial.p);
@@ -937,11 +975,12 @@ int peanut_goal_select(peanut_goal_t* g, const float* full_obstacle, const uint8
   PEANUT_HIP_CHECK(hipMemcpyAsync(val, g->out_val.p, sizeof(val), hipMemcpyDeviceToHost, s));
   if (dist_out) PEANUT_HIP_CHECK(hipMemcpyAsync(dist_out, g->dist.p, (size_t)g->H * g->W * sizeof(double), hipMemcpyDeviceToDevice, s));
   PEANUT_HIP_CHECK(hipStreamSynchronize(s));
+  if (idx[0] < 0 || idx[0] >= n) return fail(PEANUT_EHIP, "peanut_goal_select: argmax outside the local window");
   if (!idx[1] && mode != 2) {    // self.dd_wt = dd_wt (:410): the fresh weights become the last ones unless the old ones were kept
     PEANUT_HIP_CHECK(hipMemcpyAsync(g->wt_last.p, g->wt_new.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     g->last_lw = lw; g->last_lh = lh;
   }
-  g->have_last = true;
+  if (mode != 2) g->have_last = true;      // (frontier mode neither uses nor replaces the last weights)
   goal_rc_out[0] = idx[0] / lh;
   goal_rc_out[1] = idx[0] - goal_rc_out[0] * lh;
   if (stats_out) { stats_out[0] = val[0]; stats_out[1] = val[1]; stats_out[2] = idx[1]; stats_out[3] = g->last_rounds; }

@@ -25,14 +25,20 @@ def _u8(t: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
 
 
 def _ident(t):
-    """What makes two map arguments 'the same input': the storage they view (data pointer, shape, strides, dtype, device) --
-    not the Python object (full_map[0] is a new view object on every call)."""
+    """What makes two map arguments 'the same input': the storage they view (data pointer, shape, strides, dtype, device) and,
+    for a tensor, its version counter (bumped by every in-place write to the storage, through any view) -- not the Python object
+    (full_map[0] is a new view object on every call).  Only meaningful while the tensor is kept alive: a freed block can come back
+    as the storage of another tensor (``GeodesicSolver.select_begin`` holds its inputs for that reason)."""
     if t is None:
         return None
     if isinstance(t, torch.Tensor):
-        return ("t", t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
+        try:
+            version = t._version
+        except RuntimeError:      # (inference tensors carry no version counter; they cannot be written in place either)
+            version = None
+        return ("t", t.data_ptr(), tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device), version)
     a = np.asarray(t)
-    return ("n", a.__array_interface__["data"][0], a.shape, a.strides, a.dtype.str)
+    return ("n", a.__array_interface__["data"][0], a.shape, a.strides, a.dtype.str, a.tobytes())
 
 
 class GeodesicSolver:
@@ -90,7 +96,10 @@ class GeodesicSolver:
                                                     None if vis is None else vis.data_ptr(), C.byref(bounds), int(loc_rc[0]), int(loc_rc[1]),
                                                     _lib.current_stream_ptr(self.device))
         _lib.check(rc, "peanut_goal_select_begin")
-        self._begun = (tuple(_ident(t) for t in (full_obstacle, collision_map, visited_vis)), (obst, col, vis))
+        # the inputs themselves stay referenced next to their idents: a temporary (collision_map.bool()) freed here could hand its
+        # block to the next temporary, whose ident would then match with other contents
+        inputs = (full_obstacle, collision_map, visited_vis)
+        self._begun = (tuple(_ident(t) for t in inputs), (obst, col, vis), inputs)
 
     def traversible(self, full_obstacle: torch.Tensor, collision_map=None, visited_vis=None) -> torch.Tensor:
         """agent_state.py:382-386 -> uint8 [H,W] (1 = traversible)."""
@@ -134,8 +143,8 @@ class GeodesicSolver:
         """One ``update_global_goal`` evaluation -> dict(goal=(r, c), value_max, wt_sum, kept_last, rounds[, dist, value])."""
         tp = None if target_pred is None else target_pred.to(self.device, torch.float32).contiguous()
         # `begun` stays referenced until the C call has returned: the side stream may still be reading its buffers.  The inputs of
-        # select_begin are recognised by storage (data pointer, shape, strides, dtype, device), not by object identity: Agent_State
-        # passes full_map[0], a fresh view object on every call
+        # select_begin are recognised by storage (data pointer, shape, strides, dtype, device) and version counter, not by object
+        # identity: Agent_State passes full_map[0], a fresh view object on every call
         begun, self._begun = getattr(self, "_begun", None), None
         if begun is not None and begun[0] == tuple(_ident(t) for t in (full_obstacle, collision_map, visited_vis)):
             obst, col, vis = begun[1]          # the buffers select_begin handed over (a converted input is converted once)
@@ -143,6 +152,10 @@ class GeodesicSolver:
         else:
             obst = full_obstacle.to(self.device, torch.float32).contiguous()
             col, vis = _u8(collision_map, self.device), _u8(visited_vis, self.device)
+            if begun is not None and obst.data_ptr() == begun[1][0].data_ptr():
+                # the same buffer as begun but other contents (written in place since): the library recognises begun inputs by
+                # address, so it is handed a copy, which makes it drop the begun field and solve this one
+                obst = obst.clone()
         lw, lh = int(lmb[1] - lmb[0]), int(lmb[3] - lmb[2])
         if tp is not None and tuple(tp.shape) != (lw, lh):
             raise ValueError(f"target_pred must be [{lw},{lh}], got {tuple(tp.shape)}")

@@ -97,3 +97,119 @@ def test_adjacent_equal_seeds_use_the_second_order_term():
     # mirror symmetry about the pair (column c <-> 19 - c) holds to a few hundredths of a cell only: the j = -1 direction is
     # examined first and its value2 survives (the library's loop), and equal keys leave the heap in insertion order
     assert np.abs(d[:, 0:9] - d[:, 19:10:-1]).max() < 0.05
+
+
+class _StatementSelector:
+    """update_global_goal (agent_state.py:376-415) statement by statement, as oracle/goal_ref.GoalSelector.update read before it
+    was routed through select_from_field: the yardstick that routing is held to."""
+
+    def __init__(self, args, full_hw):
+        from oracle.agent_ref import disk
+        self.args, (self.full_w, self.full_h) = args, full_hw
+        self.selem = disk(int(args.col_rad))
+        self.dd_wt = None
+        self.last_global_goal = None
+        self.global_goals = None
+
+    def update(self, full_obstacle, lmb, loc_rc, target_pred, collision_map, visited_vis):
+        args = self.args
+        trav = goal_ref.traversible_map(full_obstacle, self.selem, collision_map, visited_vis)
+        r = int(np.clip(loc_rc[0] + lmb[0], 0, self.full_w - 1))
+        c = int(np.clip(loc_rc[1] + lmb[2], 0, self.full_h - 1))
+        traversible_ma = ma.masked_values(trav * 1, 0)
+        traversible_ma[r, c] = 0
+        dd = fmm_ref.distance(traversible_ma, dx=1)
+        dd = ma.filled(dd, np.max(dd) + 1)
+        dd[np.where(dd == np.max(dd))] = np.inf
+        temperature = args.dist_weight_temperature / args.map_resolution
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            dd_wt = np.exp(-dd / temperature)[lmb[0]:lmb[1], lmb[2]:lmb[3]]
+            self.wt_sum = np.sum(dd_wt)
+            if np.sum(dd_wt) < 10 and self.dd_wt is not None:
+                dd_wt = self.dd_wt
+            if args.dist_weight_temperature == -1:
+                value = target_pred
+            elif args.dist_weight_temperature == 0:
+                dd = dd.copy()
+                dd[np.where(dd < 60)] = np.inf
+                value = np.exp(-dd / 100.)[lmb[0]:lmb[1], lmb[2]:lmb[3]]
+            else:
+                value = target_pred * dd_wt
+        self.dd_wt = dd_wt
+        self.value = value
+        new_global_goal = [np.unravel_index(value.argmax(), value.shape)]
+        if new_global_goal != self.last_global_goal:
+            self.last_global_goal = self.global_goals
+            self.global_goals = new_global_goal
+        return self.global_goals
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def test_select_from_field_reproduces_update_global_goal_in_every_mode():
+    """oracle/goal_ref.select_from_field on the fmm_ref field reproduces the whole update_global_goal bit for bit -- value map,
+    weights carried to the next call, their sum, goal list -- over call sequences in every temperature mode (500; 1, where the
+    weights underflow and the stuck rule keeps the last ones; -1; 0), on a map with walls and on one without obstacles (every
+    cell reached: the farthest cells become +inf), with agent cells that need the clip, NaN in target_pred, and a reset."""
+    from types import SimpleNamespace
+    rng = np.random.RandomState(3)
+    H, W = 70, 90
+    walls = np.zeros((H, W), np.float32)
+    walls[10:50, 40] = 1.0
+    walls[30, 5:35] = 1.0
+    walls[55:60, 60:65] = 1.0
+    lmb = (6, 66, 12, 84)
+    zero = np.zeros((H, W))
+    col = zero.copy()
+    col[20, 20:30] = 1
+    for temp in (500, 1, -1, 0):
+        args = SimpleNamespace(col_rad=1, dist_weight_temperature=temp, map_resolution=5)
+        new, old = goal_ref.GoalSelector(args, (H, W)), _StatementSelector(args, (H, W))
+        calls = [(walls, (20, 10), col), (np.zeros_like(walls), (30, 40), zero), (walls, (-9, 80), zero),
+                 (walls, (70, -20), col), ("reset", None, None), (walls, (25, 30), zero)]
+        for k, (obst, loc, cm) in enumerate(calls):
+            if isinstance(obst, str):
+                new.reset()
+                old.dd_wt, old.last_global_goal, old.global_goals = None, None, None
+                continue
+            tp = rng.rand(lmb[1] - lmb[0], lmb[3] - lmb[2]).astype(np.float32)
+            if k == 2:
+                tp[7, 9] = np.nan
+            g_new = new.update(obst, lmb, loc, tp, cm, zero)
+            g_old = old.update(obst, lmb, loc, tp, cm, zero)
+            assert [tuple(int(v) for v in x) for x in g_new] == [tuple(int(v) for v in x) for x in g_old], (temp, k)
+            assert _same_bits(new.value, old.value), (temp, k)
+            assert _same_bits(new.dd_wt, old.dd_wt), (temp, k)
+            assert _same_bits(new.wt_sum, old.wt_sum), (temp, k)
+            if k == 2 and temp != 0:
+                assert tuple(int(v) for v in g_new[0]) == (7, 9), "np.argmax: the first NaN wins"
+            if k == 1 and temp == 500:
+                assert np.isinf(new.dd).sum() >= 1 and np.isfinite(new.dd).sum() < H * W, "all reached: the farthest become +inf"
+        if temp == 1:
+            assert new.kept_last is False                   # (the last call follows a reset: nothing to keep)
+
+
+def test_fixed_point_residual_restates_the_scheme():
+    """oracle/goal_ref.fmm_fixed_point_residual: on open ground the heap-ordered march (fmm_ref) and the relaxation agree, so the
+    march's own field is a fixed point of the restated update to the last bit (one seed, and several with two of them adjacent);
+    moving one cell by 1e-4 shows up in the residual, and a free cell left unreached next to reached ones is updated."""
+    trav = np.ones((40, 56), np.uint8)
+    seeds = np.zeros(trav.shape, bool)
+    seeds[13, 22] = True
+    u = goal_ref.geodesic_field(trav, (13, 22))
+    res, upd = goal_ref.fmm_fixed_point_residual(u, trav, seeds)
+    assert res.max() == 0.0 and upd[13, 22] == 0.0
+    bent = u.copy()
+    bent[20, 30] += 1e-4
+    assert goal_ref.fmm_fixed_point_residual(bent, trav, seeds)[0].max() >= 0.5e-4
+    gm = np.zeros(trav.shape, bool)
+    gm[5, 5] = gm[30, 50] = gm[31, 50] = True              # several seeds, two of them adjacent
+    u2 = goal_ref.fmm_set_multi_goal(trav, gm)
+    assert goal_ref.fmm_fixed_point_residual(u2, trav, gm)[0].max() <= 1e-12
+    # a reached cell next to an unreached free one: the update reaches it (the unreached pattern is not a fixed point)
+    holed = u.copy()
+    holed[25, 10] = np.inf
+    assert np.isfinite(goal_ref.fmm_fixed_point_residual(holed, trav, seeds)[1][25, 10])

@@ -3,7 +3,9 @@ oracle/fmm_ref.c (restated scikit-fmm, PARITY UNPINNED), oracle/goal_ref.py and 
 reference's own Agent_State.update_global_goal (tests/golden/goal_golden.npz).
 
 Gates: distance field <= 0.5 cell max-abs vs the heap-ordered oracle (measured: ~1e-12 on these maps), identical
-masked / unreachable pattern, chosen goal cell identical."""
+masked / unreachable pattern, chosen goal cell identical; the field is the fixed point of its own scheme to 1.5e-6 cell
+(oracle/goal_ref.fmm_fixed_point_residual) and the selection equals oracle/goal_ref.select_from_field on the device's field
+(value map within 2 ulp, weight sum within 1e-12 relative, same keep-last decision and goal)."""
 import os
 
 import numpy as np
@@ -38,12 +40,65 @@ def _maze(h, w, seed, density=0.012, wall_len=(10, 60)):
         else:
             trav[r:r + n, c:c + 2] = 0
     trav[rng.randint(0, h, 40), rng.randint(0, w, 40)] = 0
-    # a closed box: its inside is unreachable
-    trav[h // 4:h // 4 + 30, w // 4] = 0
-    trav[h // 4:h // 4 + 30, w // 4 + 29] = 0
-    trav[h // 4, w // 4:w // 4 + 30] = 0
-    trav[h // 4 + 29, w // 4:w // 4 + 30] = 0
+    if h >= 40 and w >= 40:
+        # a closed box: its inside is unreachable
+        trav[h // 4:h // 4 + 30, w // 4] = 0
+        trav[h // 4:h // 4 + 30, w // 4 + 29] = 0
+        trav[h // 4, w // 4:w // 4 + 30] = 0
+        trav[h // 4 + 29, w // 4:w // 4 + 30] = 0
     return trav
+
+
+def _ulp_gap(a, b):
+    """Largest distance between a and b in units of the last place (of the larger magnitude); equal NaN / inf positions count 0."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert np.array_equal(np.isnan(a), np.isnan(b)), "NaN pattern"
+    ok = ~np.isnan(a)
+    a, b = a[ok], b[ok]
+    same = a == b
+    if same.all():
+        return 0.0
+    a, b = a[~same], b[~same]
+    assert np.isfinite(a).all() and np.isfinite(b).all(), "infinite on one side only"
+    return float((np.abs(a - b) / np.spacing(np.maximum(np.abs(a), np.abs(b)))).max())
+
+
+def _select_and_check(sol, last, obst, col, vis, lmb, loc, tp, temperature, map_resolution=5):
+    """One ``select`` held to oracle/goal_ref.select_from_field applied to the device's own field: value map within 2 ulp, sum of
+    the weights within 1e-12 relative, the keep-last decision equal, the goal cell equal (unless the two best reference values are
+    within 1e-15 relative: then one of them).  ``last`` = the weights the restatement carries from the previous call (``dd_wt``);
+    returns (device result, the weights carried to the next call).  The device forgets the last weights when the window changes
+    size (the reference would fail to broadcast them), and at temperature 0 -- where the reference's weights exp(-dd / 0) are
+    never used -- it reports the sum of the frontier values and leaves the last weights alone."""
+    from oracle import goal_ref
+    lw, lh = lmb[1] - lmb[0], lmb[3] - lmb[2]
+    if last is not None and last.shape != (lw, lh):
+        last = None
+    got = sol.select(obst, col, vis, lmb, loc, tp, temperature, map_resolution, want_dist=True, want_value=True)
+    dd = got["dist"].cpu().numpy()
+    tpn = None if tp is None else tp.detach().cpu().numpy().astype(np.float32)
+    goal, value, wt_sum, kept, new_last = goal_ref.select_from_field(dd, lmb, tpn, temperature, map_resolution, last)
+    v = got["value"].cpu().numpy()
+    assert _ulp_gap(v, value) <= 2, f"value map: {_ulp_gap(v, value)} ulp"
+    if temperature == 0:
+        assert not got["kept_last"]
+        wt_sum, new_last = float(np.sum(value)), last
+    else:
+        assert got["kept_last"] == kept, (got["kept_last"], kept, wt_sum)
+    if np.isfinite(wt_sum) and wt_sum != 0.0:
+        assert abs(got["wt_sum"] - wt_sum) <= 1e-12 * abs(wt_sum), (got["wt_sum"], wt_sum)
+    else:
+        assert got["wt_sum"] == wt_sum or (np.isnan(got["wt_sum"]) and np.isnan(wt_sum)), (got["wt_sum"], wt_sum)
+    flat = value.ravel()
+    top = flat[np.argmax(flat)]
+    if got["goal"] != goal:
+        assert np.isfinite(top) and top != 0.0
+        near = np.flatnonzero(np.abs(flat - top) <= 1e-15 * abs(top))
+        assert near.size >= 2 and np.ravel_multi_index(got["goal"], value.shape) in near, (got["goal"], goal)
+    r, c = got["goal"]
+    assert 0 <= r < lw and 0 <= c < lh
+    assert np.array_equal(np.float64(got["value_max"]), v[r, c], equal_nan=True)
+    return got, new_last
 
 
 def _oracle_field(trav, seeds):
@@ -220,29 +275,26 @@ def test_goal_selection_episode_matches_reference(golden_dir):
 def test_update_state_selects_goals_and_keeps_last_weights_when_stuck():
     """Agent_State.update_state with goal selection on (default): update_prediction -> update_global_goal; an agent
     walled in by obstacles (sum of weights < 10) keeps the previous weights (agent_state.py:398-399)."""
-    from oracle.agent_ref import agent_args
     from peanut_amd.goal import GeodesicSolver
     sol = GeodesicSolver(96, 96, 1)
-    obst = torch.zeros((96, 96))
+    obst = torch.zeros((96, 96))           # no obstacle: every cell is reached, the farthest ones weigh 0 (:393)
     tp = torch.zeros((48, 48))
     tp[40, 40] = 1.0
     tp[3, 3] = 0.8
     lmb = (24, 72, 24, 72)
-    r1 = sol.select(obst, None, None, lmb, (10, 10), tp, 500.0, 5, want_value=True)
-    assert not r1["kept_last"] and r1["wt_sum"] > 10 and r1["goal"] in ((40, 40), (3, 3))
+    r1, last = _select_and_check(sol, None, obst, None, None, lmb, (10, 10), tp, 500.0)
+    assert not r1["kept_last"] and r1["wt_sum"] > 10
     v1 = r1["value"].cpu()
     obst2 = obst.clone()
     obst2[24 + 10 - 3:24 + 10 + 4, 24 + 10 - 3:24 + 10 + 4] = 1.0       # the agent's cell and its surroundings are blocked
-    r2 = sol.select(obst2, None, None, lmb, (10, 10), tp, 500.0, 5, want_value=True)
+    r2, last = _select_and_check(sol, last, obst2, None, None, lmb, (10, 10), tp, 500.0)
     assert r2["kept_last"] and r2["wt_sum"] < 10 and r2["goal"] == r1["goal"] and torch.equal(r2["value"].cpu(), v1)
     sol.reset()
-    r3 = sol.select(obst2, None, None, lmb, (10, 10), tp, 500.0, 5)
+    r3, last = _select_and_check(sol, None, obst2, None, None, lmb, (10, 10), tp, 500.0)
     assert not r3["kept_last"]                                            # nothing to fall back to after reset
-    r4 = sol.select(obst, None, None, lmb, (10, 10), tp, -1, 5)           # temperature -1: target_pred alone
+    r4, last = _select_and_check(sol, last, obst, None, None, lmb, (10, 10), tp, -1.0)    # temperature -1: target_pred alone
     assert r4["goal"] == (40, 40)
-    r5 = sol.select(obst, None, None, lmb, (10, 10), None, 0, 5)          # temperature 0: frontier mode, no target_pred
-    gr, gc = r5["goal"]
-    assert 59.0 <= np.hypot(gr - 10, gc - 10) or r5["value_max"] == 0.0
+    _select_and_check(sol, last, obst, None, None, lmb, (10, 10), None, 0.0)              # temperature 0: frontier mode
 
 
 @pytest.mark.parametrize("shape,seed", [((960, 960), 1), ((480, 480), 2)], ids=lambda v: str(v))
@@ -313,7 +365,7 @@ def test_field_solved_next_to_the_prediction_forward_is_the_same_field():
         sol2.reset()
         sol2.select_begin(obst, col, vis, lmb, loc)
         got = sol2.select(obst, col, vis, lmb, loc, produce_target(), 500.0, 5, want_dist=True, want_value=True)
-        assert got["goal"] == ref["goal"] and abs(got["wt_sum"] - ref["wt_sum"]) <= 1e-9 * ref["wt_sum"] and got["rounds"] >= 1      # (the sum is an atomic accumulation: last digits vary)
+        assert got["goal"] == ref["goal"] and got["wt_sum"] == ref["wt_sum"] and got["rounds"] >= 1      # (the sum is reduced in a fixed order)
         assert torch.equal(got["dist"], ref["dist"]) and torch.equal(got["value"], ref["value"])
     # an input that has to be converted (bool -> uint8) is converted once, at the begin, and the select reuses the buffer
     sol2.reset()
@@ -350,7 +402,8 @@ def test_field_solved_next_to_the_prediction_forward_is_the_same_field():
 
 def test_update_state_with_and_without_the_overlapped_field_agree():
     """Agent_State.update_state marks the goal solver's inputs before the prediction forward (goal_overlap, default on): the
-    episode's goals, prediction schedule and final map equal those of the serial order."""
+    episode's goals, prediction schedule and final map equal those of the serial order, and the overlap is taken on every
+    prediction step (``begun_matches``)."""
     from oracle import mapping_scenes
     from oracle.agent_ref import agent_args, fake_pattern
     from peanut_amd.agent_state import Agent_State
@@ -369,6 +422,8 @@ def test_update_state_with_and_without_the_overlapped_field_agree():
             if st.update_state(obs, infos):
                 steps.append(i)
                 goals.append(tuple(st.global_goals[0]))
+                # every prediction step's select takes over the field its select_begin started (none without the overlap)
+                assert st._goal.begun_matches == (len(steps) if overlap else 0), (overlap, i)
         runs.append((steps, goals, st.full_map.clone(), st.value_max))
     assert len(runs[0][0]) >= 2
     assert runs[0][0] == runs[1][0] and runs[0][1] == runs[1][1] and runs[0][3] == runs[1][3]
@@ -407,3 +462,212 @@ def test_real_prediction_forward_next_to_the_goal_field_is_bit_identical(precisi
     assert len(runs[0][0]) >= 2 and runs[0][0] == runs[1][0]
     assert all(torch.equal(a, b) for a, b in zip(runs[0][1], runs[1][1]))
     assert torch.equal(runs[0][2], runs[1][2])
+
+
+def _obstacles(h, w, seed):
+    """A full_map[0]-like obstacle map (values around the rint threshold) with the maze's walls."""
+    rng = np.random.RandomState(seed)
+    obst = (~_maze(h, w, seed).astype(bool)).astype(np.float32) * rng.choice([0.51, 1.0, 2.0], size=(h, w)).astype(np.float32)
+    obst += (rng.rand(h, w) < 0.01).astype(np.float32) * 0.49          # below the threshold: free
+    return torch.from_numpy(obst)
+
+
+@pytest.mark.parametrize("temperature", [500.0, 1.0, -1.0, 0.0])
+def test_selection_matches_the_restatement_on_the_device_field(temperature):
+    """update_global_goal from the field onward, against oracle/goal_ref.select_from_field on the device's own field, over one
+    episode-like sequence of calls per temperature (500; 1: the weights underflow, the stuck rule keeps the last ones; -1: target_pred
+    alone; 0: frontier mode): a non-square full map and window, windows touching each border of the map, agent cells outside the map
+    (np.clip), a map without obstacles (every cell reached: the farthest cells weigh 0), NaN in target_pred, and a reset."""
+    from peanut_amd.goal import GeodesicSolver
+    H, W = 200, 264
+    sol = GeodesicSolver(H, W, 2)
+    g = torch.Generator().manual_seed(int(temperature) + 7)
+    obst = _obstacles(H, W, 11)
+    col = torch.zeros((H, W), dtype=torch.uint8)
+    col[100, 40:60] = 1
+    vis = torch.zeros((H, W), dtype=torch.uint8)
+    vis[60:70, 100:140] = 1
+    empty = torch.zeros((H, W))
+    calls = [  # (obstacles, lmb = (gx1, gx2, gy1, gy2), agent cell in the window)
+        (obst, (50, 150, 70, 190), (50, 60)),         # inside, 100 x 120
+        (obst, (0, 100, 70, 190), (30, 20)),          # top border
+        (obst, (100, 200, 70, 190), (80, 100)),       # bottom border
+        (obst, (50, 150, 0, 120), (-70, 50)),         # left border; agent above the map (clipped)
+        (obst, (50, 150, 144, 264), (40, 200)),       # right border; agent right of the map (clipped)
+        (empty, (50, 150, 70, 190), (50, 60)),        # no obstacles
+        (empty, (100, 200, 144, 264), (-300, -300)),  # ... agent clipped to (0, 0): the map's farthest cell is in the window
+        ("nan", (50, 150, 70, 190), (50, 60)),        # one NaN in target_pred
+        ("reset", None, None),
+        (obst, (0, 200, 0, 264), (100, 130)),         # the whole map as the window
+        (obst, (30, 90, 10, 250), (20, 100)),         # 60 x 240
+    ]
+    last = None
+    for k, (ob, lmb, loc) in enumerate(calls):
+        if isinstance(ob, str) and ob == "reset":
+            sol.reset()
+            last = None
+            continue
+        tp = torch.rand((lmb[1] - lmb[0], lmb[3] - lmb[2]), generator=g)
+        if isinstance(ob, str):
+            ob = obst
+            tp[37, 61] = float("nan")
+        plain = ob is empty                            # no obstacle, no collision: no masked cell at all
+        got, last = _select_and_check(sol, last, ob.cuda(), None if plain else col.cuda(), None if plain else vis.cuda(), lmb, loc,
+                                      tp.cuda(), temperature)
+        if isinstance(calls[k][0], str) and temperature != 0:
+            assert got["goal"] == (37, 61), "np.argmax: the first NaN"
+        if ob is empty:
+            assert np.isfinite(got["dist"].cpu().numpy()).all()
+            if lmb[0] == 100 and temperature in (500.0, 0.0):
+                assert got["value"][-1, -1].item() == 0.0 and got["value"][-2, -1].item() > 0.0, "the farthest cell weighs 0 (:393)"
+
+        if temperature == 1.0 and k in (1, 2, 3, 4, 5, 6):
+            assert got["kept_last"], "temperature 1: the weights underflow and the last ones are kept"
+
+
+@pytest.mark.parametrize("temperature", [-1.0, 500.0])
+def test_argmax_plateaus_and_nan_over_a_window_of_many_workgroups(temperature):
+    """A window larger than 256 x 1024 cells (the argmax's grid strides over it): an all-zero target_pred, equal maxima handled by
+    different workgroups and by one lane in consecutive strides (temperature -1: exact ties, the first index wins), one NaN, and
+    all NaN -- the goal is then the first cell, never a cell outside the window."""
+    from peanut_amd.goal import GeodesicSolver
+    H, W = 560, 600
+    sol = GeodesicSolver(H, W, 1)
+    obst = torch.zeros((H, W), device="cuda")
+    obst[200:202, 100:500] = 1.0
+    lmb = (10, 550, 40, 540)                        # 540 x 500 = 270000 cells > 262144
+    lw, lh = lmb[1] - lmb[0], lmb[3] - lmb[2]
+    loc = (300, 250)
+    last = None
+    tp = torch.zeros((lw, lh))
+    got, last = _select_and_check(sol, last, obst, None, None, lmb, loc, tp.cuda(), temperature)
+    # (workgroup, lane) of an index: ((i % 262144) // 256, i % 256); the first index, 300, is workgroup 1's, another maximum
+    # sits in workgroup 0's second stride, one in a later workgroup, and one behind 300 in the same lane's next stride
+    tp.view(-1)[[262144 + 10, 5000, 300, 262144 + 300]] = 0.75
+    got, last = _select_and_check(sol, last, obst, None, None, lmb, loc, tp.cuda(), temperature)
+    if temperature == -1.0:
+        assert got["goal"] == divmod(300, lh)
+    one = torch.rand((lw, lh), generator=torch.Generator().manual_seed(2))
+    one.view(-1)[262144 + 77] = float("nan")
+    one.view(-1)[200000] = float("nan")
+    got, last = _select_and_check(sol, last, obst, None, None, lmb, loc, one.cuda(), temperature)
+    assert got["goal"] == divmod(200000, lh)
+    alln = torch.full((lw, lh), float("nan"))
+    got, last = _select_and_check(sol, last, obst, None, None, lmb, loc, alln.cuda(), temperature)
+    assert got["goal"] == (0, 0) and np.isnan(got["value_max"])
+
+
+FIXED_POINT_GATE = 1.5e-6    # cells: stage B's 1e-6-cell noise threshold + the single-precision solve; measured maximum 1.25e-6
+
+
+@pytest.mark.parametrize("shape,seed", [((960, 960), 21), ((480, 480), 22), ((250, 333), 23), ((31, 33), 24), ((7, 300), 25)],
+                         ids=lambda v: str(v))
+def test_fmm_field_is_the_fixed_point_of_its_scheme(shape, seed):
+    """The returned field IS the fixed point of the scheme goal.hip solves, not merely within 0.5 cell of the heap-ordered march:
+    one float64 stage-B update of every cell on the graph ordered by the field itself (oracle/goal_ref.fmm_fixed_point_residual)
+    moves no reached cell by more than the gate, and the reached cells are exactly the 4-connected components of the traversible
+    map that hold a seed.  One seed, and a goal mask with several seeds (one on a masked cell)."""
+    from scipy import ndimage as ndi
+    from oracle import goal_ref
+    from peanut_amd.goal import GeodesicSolver
+    h, w = shape
+    trav = _maze(h, w, seed)
+    rng = np.random.RandomState(seed)
+    src = (h // 2, w // 2 - 1)
+    trav[max(src[0] - 2, 0):src[0] + 3, max(src[1] - 2, 0):src[1] + 3] = 1
+    gm = np.zeros((h, w), np.uint8)
+    gm[rng.randint(0, h, 4), rng.randint(0, w, 4)] = 1
+    gm[src] = 0
+    ys, xs = np.nonzero(gm)
+    trav[ys[0], xs[0]] = 0                              # a goal on a masked cell
+    sol = GeodesicSolver(h, w, 0)
+    worst = 0.0
+    for goal, mask in ((src, None), (None, gm)):
+        u = sol.distance(torch.from_numpy(trav), goal=goal, goal_mask=None if mask is None else torch.from_numpy(mask)).cpu().numpy()
+        assert sol.converged
+        seeds = np.zeros((h, w), bool)
+        if mask is None:
+            seeds[goal] = True
+        else:
+            seeds |= mask == 1
+        labels, _ = ndi.label((trav != 0) | seeds)      # (default structure: 4-connected)
+        reach = np.isin(labels, np.unique(labels[seeds]))
+        assert np.array_equal(np.isfinite(u), reach), "reached cells = the seeds' components"
+        assert (u[seeds] == 0).all()
+        res, _ = goal_ref.fmm_fixed_point_residual(u, trav, seeds)
+        worst = max(worst, float(res.max()))
+        print(f"{h}x{w} {'goal cell' if mask is None else 'goal mask'}: fixed-point residual max {res.max():.3e} cells "
+              f"over {int(reach.sum())} reached cells ({sol.passes} ordering passes)")
+    assert worst <= FIXED_POINT_GATE
+
+
+def test_select_begin_on_reused_storage_or_edited_inputs_solves_the_new_inputs():
+    """select_begin recognises the select that continues its work by the inputs' storage.  A temporary input (collision.bool())
+    whose block the allocator could hand to the next temporary, and an input written in place between the two calls, must not
+    make the select reuse the begun field: the result equals that of a select alone (the test says whether the allocator reused
+    the block)."""
+    from peanut_amd.goal import GeodesicSolver
+    H = W = 240
+    obst = _obstacles(H, W, 31).cuda()
+    lmb, loc = (40, 200, 40, 200), (80, 80)
+    obst[40 + 70:40 + 90, 40 + 70:40 + 90] = 0.0        # the agent's surroundings are free
+    col_a = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+    col_b = col_a.clone()
+    col_b[40 + 60:40 + 100, 40 + 90] = 1                 # a wall next to the agent: another field
+    vis = torch.zeros((H, W), dtype=torch.uint8, device="cuda")
+    tp = torch.rand((160, 160), generator=torch.Generator().manual_seed(3)).cuda()
+    alone = GeodesicSolver(H, W, 1)
+    sol = GeodesicSolver(H, W, 1)
+
+    def begin_on_a_temporary():
+        t = col_a.bool()
+        sol.select_begin(obst, t, vis, lmb, loc)
+        return t.data_ptr()
+
+    ptr_a = begin_on_a_temporary()
+    tb = col_b.bool()
+    reused = tb.data_ptr() == ptr_a
+    got = sol.select(obst, tb, vis, lmb, loc, tp, 500.0, 5, want_dist=True, want_value=True)
+    ref = alone.select(obst, tb, vis, lmb, loc, tp, 500.0, 5, want_dist=True, want_value=True)
+    print(f"allocator handed the begun temporary's block to the next one: {reused}")
+    assert torch.equal(got["dist"], ref["dist"]) and got["goal"] == ref["goal"] and got["wt_sum"] == ref["wt_sum"]
+    # written in place between select_begin and select (obstacles and collision map already in the library's formats)
+    obst2, col2 = obst.clone(), col_a.clone()
+    sol.reset()
+    alone.reset()
+    sol.select_begin(obst2, col2, vis, lmb, loc)
+    obst2[40 + 60:40 + 100, 40 + 70] = 1.0
+    got = sol.select(obst2, col2, vis, lmb, loc, tp, 500.0, 5, want_dist=True)
+    ref = alone.select(obst2, col2, vis, lmb, loc, tp, 500.0, 5, want_dist=True)
+    assert torch.equal(got["dist"], ref["dist"]) and got["goal"] == ref["goal"]
+    # ... through a view of a larger map (Agent_State passes full_map[0]): the view shares the map's version counter
+    full = torch.stack([obst, obst * 0])
+    sol.select_begin(full[0], col2, vis, lmb, loc)
+    full[0, 40 + 75, 40 + 60:40 + 100] = 1.0
+    got = sol.select(full[0], col2, vis, lmb, loc, tp, 500.0, 5, want_dist=True)
+    ref = alone.select(full[0], col2, vis, lmb, loc, tp, 500.0, 5, want_dist=True)
+    assert torch.equal(got["dist"], ref["dist"]) and got["goal"] == ref["goal"]
+    n0 = sol.begun_matches
+    sol.select_begin(full[0], col2, vis, lmb, loc)          # unchanged inputs: the begun field is taken over
+    got = sol.select(full[0], col2, vis, lmb, loc, tp, 500.0, 5, want_dist=True)
+    assert sol.begun_matches == n0 + 1 and torch.equal(got["dist"], ref["dist"])
+
+
+def test_selection_is_deterministic():
+    """Repeated selects on the same inputs: the same sum of weights, value map and goal, bit for bit (the sum decides the
+    keep-last rule, so it must not vary in its last digits)."""
+    from peanut_amd.goal import GeodesicSolver
+    H = W = 960
+    obst = _obstacles(H, W, 41).cuda()
+    obst[470:490, 470:490] = 0.0
+    tp = torch.rand((960, 960), generator=torch.Generator().manual_seed(4)).cuda()
+    sol = GeodesicSolver(H, W, 1)
+    first = None
+    for _ in range(6):
+        sol.reset()
+        got = sol.select(obst, None, None, (0, 960, 0, 960), (480, 480), tp, 500.0, 5, want_value=True)
+        key = (got["goal"], np.float64(got["wt_sum"]).tobytes(), np.float64(got["value_max"]).tobytes())
+        if first is None:
+            first, v0 = key, got["value"]
+        assert key == first
+        assert torch.equal(got["value"], v0)
