@@ -259,8 +259,34 @@ int peanut_map_forward(peanut_map_t* h, const float* obs, const float* pose_obs,
 int peanut_map_mark_agent(float* local_map, int channels, int m, int r0, int r1, int c0, int c1, const uint8_t* selem,
                           int selem_radius, int n_centres, const int* centres_rc, void* stream);
 /* hipGraph replay of the step's launches, keyed on the seven pointer/stream arguments (an agent ping-pongs two map
- * buffers: two cached graphs). */
+ * buffers: two cached graphs).  Applies to peanut_map_forward only: the batched call below always enqueues plainly. */
 int peanut_map_use_graph(peanut_map_t* h, int enable);
+
+/* ---- several episodes per step (the reference runs one process per environment on a shared card, nav/collect.py:32-50) ---- */
+#define PEANUT_MAP_MAX_BATCH 16
+/* Allocates max_batch (1..PEANUT_MAP_MAX_BATCH) slots of the per-frame scratch that the create call allocates once, each
+ * initialised as that one is; a call with max_batch at or below what is reserved does nothing.  The slots are separate
+ * from the single step's scratch, so single and batched steps on one handle do not disturb each other.  Synchronous:
+ * all of the batched path's allocation happens here, none while stepping. */
+int peanut_map_reserve(peanut_map_t* h, int max_batch);
+/* Semantic_Mapping.forward (mapping.py:52-179) for E independent episodes in the launches of ONE single-episode step (8;
+ * 9 with du_scale > 1): the episode is a grid dimension and every kernel runs the single step's own code on that
+ * episode's scratch slot, so per episode every output is bit-identical to the single-episode call above on the same inputs.
+ * obs [E,C,h,w], pose_obs [E,3], poses_inout [E,3] (in place), fp_map_pred [E,V,V]: device fp32, contiguous.  maps_last /
+ * map_pred: HOST arrays of E device pointers, each [C,M,M] (every episode owns its map tensors; they go to the kernels by
+ * value).  Refused with PEANUT_EINVAL, nothing enqueued: E above the reserved batch, a null pointer, a map_pred that is
+ * also some episode's maps_last, two episodes sharing one map_pred.  No host sync, no graph replay. */
+int peanut_map_forward_batch(peanut_map_t* h, int E, const float* obs, const float* pose_obs, const float* const* maps_last,
+                             float* poses_inout, float* fp_map_pred, float* const* map_pred, void* stream);
+/* The bookkeeping of the single-map call above (nav/agent/agent_state.py:281-296) for E maps in one launch.  local_maps: host
+ * array of E distinct device pointers, each [channels, m, m]; squares: host [E,4] = (r0, r1, c0, c1) per episode; n_centres:
+ * host [E]; centres_rc: host [E,2,2].  The single call's checks are applied to every episode before anything is enqueued:
+ * one refused episode refuses the whole call and leaves every map as it was. */
+int peanut_map_mark_agent_batch(int E, float* const* local_maps, int channels, int m, const int* squares, const uint8_t* selem,
+                                int selem_radius, const int* n_centres, const int* centres_rc, void* stream);
+/* Test hook: kernels enqueued by the handle's most recent forward call, single or batched (counted on the host beside the
+ * launches); -1 for a null handle. */
+int peanut_map_debug_launches(peanut_map_t* h);
 
 /* ------------------------------------------------------------------------------------------
  * Stage 1 -- Mask R-CNN front end (preprocessing + ResNet-FPN backbone + RPN head)
@@ -414,6 +440,10 @@ int peanut_paste_masks(const float* masks, const float* boxes, int n, int M, int
  * [0,1] (0 = invalid), sem [H,W,ncat] fp32 -> obs [3+1+ncat, H/ds, W/ds] fp32. */
 int peanut_preprocess_obs(const uint8_t* rgb, const float* depth, const float* sem, int H, int W, int ncat, int ds,
                           double min_d, double max_d, float* obs, void* stream);
+/* The same (agent_helper.py:175-217) for E frames (1..PEANUT_MAP_MAX_BATCH) in one launch: rgb [E,H,W,3], depth [E,H,W],
+ * sem [E,H,W,ncat] -> obs [E, 3+1+ncat, H/ds, W/ds], each frame bit-identical to the single call. */
+int peanut_preprocess_obs_batch(const uint8_t* rgb, const float* depth, const float* sem, int E, int H, int W, int ncat, int ds,
+                                double min_d, double max_d, float* obs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stage 1 -- per-instance mask accumulation of SemanticPredMaskRCNN.get_prediction

@@ -185,9 +185,18 @@ class Agent_State:
 
     # ---- agent_state.py:268-300 ----
     def update_local_map(self, obs):
-        args = self.args
         self._map_step(obs)
         locs = self.local_pose.cpu().numpy()
+        loc_r, loc_c, traj_rad, centres = self._local_map_host(locs)
+        self._mark_agent(loc_r, loc_c, traj_rad, centres)
+        self.loc_r = loc_r
+        self.loc_c = loc_c
+
+    def _local_map_host(self, locs):
+        """The host decisions of ``update_local_map`` (:276-291) from the pose that was read back: planner pose, agent cell,
+        distance to the goal, and what to mark -- (loc_r, loc_c, traj_rad, centres) for ``_mark_agent``.  Shared by the
+        single-episode step above and ``Agent_State_Group``, which reads the poses of all its episodes back at once."""
+        args = self.args
         self.planner_pose_inputs[:3] = locs + self.origins
         r, c = locs[1], locs[0]
         loc_r = int(r * 100.0 / args.map_resolution)
@@ -198,9 +207,7 @@ class Agent_State:
         centres = [(loc_r, loc_c)]
         if self.dist_to_goal < args.goal_reached_dist:
             centres.append((self.global_goals[0][0], self.global_goals[0][1]))
-        self._mark_agent(loc_r, loc_c, traj_rad, centres)
-        self.loc_r = loc_r
-        self.loc_c = loc_c
+        return loc_r, loc_c, traj_rad, centres
 
     def _upload_pose(self, sensor_pose):
         """``torch.from_numpy(np.asarray(infos['sensor_pose'])).float().to(device)`` (:225) through one pinned buffer: the copy is
@@ -218,6 +225,15 @@ class Agent_State:
                                                                    # for (r, c) in centres: the agent, and the goal once reached
 
         with Python's slice clamping and torch's index rules (negative wraps, out of range raises IndexError)."""
+        lm, m, rad, (r0, r1, c0, c1) = self._mark_args(loc_r, loc_c, traj_rad, centres)
+        flat = (C.c_int * (2 * len(centres)))(*[int(v) for rc in centres for v in rc])
+        with torch.cuda.device(self.device):
+            rc = _lib.load().peanut_map_mark_agent(lm.data_ptr(), int(lm.shape[0]), m, r0, r1, c0, c1, self._selem_mask.data_ptr(), rad,
+                                                   len(centres), C.byref(flat), _lib.current_stream_ptr(self.device))
+        _lib.check(rc, "peanut_map_mark_agent")
+
+    def _mark_args(self, loc_r, loc_c, traj_rad, centres):
+        """The checks of ``_mark_agent`` and the normalised trajectory square: (local_map, m, footprint radius, (r0, r1, c0, c1))."""
         lm = self.local_map
         if not lm.is_contiguous():            # (a view into full_map right after _rebind_local; _map_step replaces it)
             raise RuntimeError("local_map must be contiguous here")
@@ -232,11 +248,7 @@ class Agent_State:
         for cr, cc in centres:
             if cr - rad < -m or cr + rad >= m or cc - rad < -m or cc + rad >= m:
                 raise IndexError(f"explored-area footprint around ({cr}, {cc}) leaves the {m} x {m} local map")
-        flat = (C.c_int * (2 * len(centres)))(*[int(v) for rc in centres for v in rc])
-        with torch.cuda.device(self.device):
-            rc = _lib.load().peanut_map_mark_agent(lm.data_ptr(), int(lm.shape[0]), m, r0, r1, c0, c1, self._selem_mask.data_ptr(), rad,
-                                                   len(centres), C.byref(flat), _lib.current_stream_ptr(self.device))
-        _lib.check(rc, "peanut_map_mark_agent")
+        return lm, m, rad, (r0, r1, c0, c1)
 
     # ---- agent_state.py:303-338 ----
     def update_full_map(self):
@@ -251,6 +263,12 @@ class Agent_State:
 
     # ---- agent_state.py:345-373, on the device ----
     def update_prediction(self, goal_follows=False):
+        crop = self._prediction_input(goal_follows)
+        self._prediction_output(self.prediction_model.get_prediction_batch(crop)[0])
+
+    def _prediction_input(self, goal_follows=False):
+        """First half of ``update_prediction``: the local map written back, the goal solver begun, and the [1,C,W,W] window the
+        prediction model reads (the whole full map, or its centre crop)."""
         args = self.args
         self.full_map[:, self.lmb[0]:self.lmb[1], self.lmb[2]:self.lmb[3]] = self.local_map
         if goal_follows and getattr(args, "goal_overlap", True):
@@ -258,14 +276,23 @@ class Agent_State:
             # the prediction -- begun here, the solver runs it on its own stream beside the forward below (include/peanut_hip.h)
             self._goal_solver().select_begin(self.full_map[0], self.collision_map, self.visited_vis, self.lmb, (self.loc_r, self.loc_c))
         if self.full_w == args.prediction_window and self.full_h == args.prediction_window:
-            object_preds = self.prediction_model.get_prediction_batch(self.full_map[None].contiguous())[0]
+            return self.full_map[None].contiguous()
+        x1 = self.full_w // 2 - args.prediction_window // 2
+        x2 = x1 + args.prediction_window
+        y1 = self.full_h // 2 - args.prediction_window // 2
+        y2 = y1 + args.prediction_window
+        return self.full_map[:, x1:x2, y1:y2].contiguous()[None]
+
+    def _prediction_output(self, preds):
+        """Second half of ``update_prediction``: ``preds`` [K,W,W] of this episode's window -> ``target_pred``."""
+        args = self.args
+        if self.full_w == args.prediction_window and self.full_h == args.prediction_window:
+            object_preds = preds
         else:
             x1 = self.full_w // 2 - args.prediction_window // 2
             x2 = x1 + args.prediction_window
             y1 = self.full_h // 2 - args.prediction_window // 2
             y2 = y1 + args.prediction_window
-            crop = self.full_map[:, x1:x2, y1:y2].contiguous()[None]
-            preds = self.prediction_model.get_prediction_batch(crop)[0]
             object_preds = torch.zeros((preds.shape[0], self.full_w, self.full_h), dtype=preds.dtype,
                                        device=preds.device)
             object_preds[:, x1:x2, y1:y2] = preds
@@ -312,17 +339,202 @@ class Agent_State:
         self.goal_cat = infos['goal_cat_id']
         self.poses = self._upload_pose(infos['sensor_pose'])
         self.update_local_map(obs)
-        if self.l_step == args.num_local_steps - 1:
-            self.l_step = 0
-            self.update_full_map()
+        self._step_full_map()
         predicted = False
-        if (self.step % args.update_goal_freq == args.update_goal_freq - 1 or self.step == 0 or
-                self.dist_to_goal < args.goal_reached_dist) and self.step >= args.switch_step \
-                and self.prediction_model is not None:
+        if self._prediction_due():
             select = getattr(args, "select_goal", True)
             self.update_prediction(goal_follows=select)
             if select:
                 self.update_global_goal()
             predicted = True
         self.inc_step()
+        return predicted
+
+    def _step_full_map(self):
+        """(:231-235) the local period: every ``num_local_steps`` steps the local map goes back into the full map."""
+        if self.l_step == self.args.num_local_steps - 1:
+            self.l_step = 0
+            self.update_full_map()
+
+    def _prediction_due(self):
+        """(:240) whether this step predicts and selects a goal."""
+        args = self.args
+        return (self.step % args.update_goal_freq == args.update_goal_freq - 1 or self.step == 0 or
+                self.dist_to_goal < args.goal_reached_dist) and self.step >= args.switch_step \
+            and self.prediction_model is not None
+
+
+class Agent_State_Group:
+    """E ``Agent_State`` objects on one device stepped in lock-step, so that the map projection sees a batch of E: the
+    one-process counterpart of the reference's several environments per GPU (nav/collect.py:32-50, ``--sem_gpu_id``).
+
+    Per step: one pinned ``[E,3]`` pose upload, one ``Semantic_Mapping.forward_batch``, ONE ``[E,3]`` pose read-back, the host
+    decisions of ``update_local_map`` per episode, one ``peanut_map_mark_agent_batch``, then per episode exactly what
+    ``Agent_State.update_state`` does afterwards.  Every episode ends a step with the bits it would have stepping alone.
+    ``batch_predictions=True`` runs the episodes that predict on the same step through one ``get_prediction_batch`` call; a
+    batched forward differs from batch 1 in the last fp32 bits, hence opt-in.
+
+    The states share one ``Semantic_Mapping`` handle, reserved for ``max_batch`` episodes (default: all of them).  The batch
+    is ``self.active``, in order; ``drop`` takes an episode out (it ended), ``reset_active`` puts all back."""
+
+    MAP_FIELDS = ("frame_height", "frame_width", "map_resolution", "map_size_cm", "global_downscaling", "vision_range", "hfov",
+                  "du_scale", "cat_pred_threshold", "exp_pred_threshold", "map_pred_threshold", "num_sem_categories",
+                  "camera_height", "col_rad")
+
+    def __init__(self, states, max_batch=None, batch_predictions=False):
+        states = list(states)
+        if not states:
+            raise ValueError("Agent_State_Group needs at least one state")
+        max_batch = len(states) if max_batch is None else int(max_batch)
+        if not 1 <= max_batch <= Semantic_Mapping.MAX_BATCH:
+            raise ValueError(f"max_batch must be 1..{Semantic_Mapping.MAX_BATCH}, got {max_batch}")
+        if len(states) > max_batch:
+            raise ValueError(f"{len(states)} episodes exceed the reserve of {max_batch}")
+        if len({id(s) for s in states}) != len(states):
+            raise ValueError("the same Agent_State appears twice")
+        first = states[0]
+        for e, s in enumerate(states[1:], 1):
+            if s.device != first.device:
+                raise ValueError(f"state {e} lives on {s.device}, state 0 on {first.device}")
+            diff = [f for f in self.MAP_FIELDS if getattr(s.args, f) != getattr(first.args, f)]
+            if diff:
+                raise ValueError(f"state {e} differs from state 0 in the mapping arguments {diff}")
+        self.states = states
+        self.active = list(states)
+        self.device = first.device
+        self.batch_predictions = bool(batch_predictions)
+        self.sem_map_module = first.sem_map_module
+        self.sem_map_module.reserve(max_batch)
+        for s in states:
+            s.sem_map_module = self.sem_map_module
+        self.max_batch = max_batch
+        self._poses_host = self._pinned(max_batch)
+
+    # ---- the device calls (everything else in this class is host logic) ----
+    @staticmethod
+    def _pinned(n):
+        return torch.zeros((n, 3), dtype=torch.float32).pin_memory()
+
+    def _upload_poses(self, sensor_poses):
+        """E sensor poses through one pinned buffer, one asynchronous copy (``Agent_State._upload_pose`` for the batch)."""
+        E = len(sensor_poses)
+        self._poses_host[:E].copy_(torch.from_numpy(np.asarray(sensor_poses, dtype=np.float64).reshape(E, 3)).float())
+        return self._poses_host[:E].to(self.device, non_blocking=True)
+
+    def _map_step(self, obs, poses):
+        """One ``forward_batch`` over the active episodes; the one pose read-back of the step.  Returns locs [E,3] (host)."""
+        act = self.active
+        maps_last = [s.local_map if s.local_map.is_contiguous() else s.local_map.contiguous() for s in act]
+        local_poses = torch.stack([s.local_pose for s in act])
+        _, map_pred, _, local_poses = self.sem_map_module.forward_batch(obs, poses, maps_last, local_poses)
+        for e, s in enumerate(act):
+            s.poses = poses[e]
+            s.local_map = map_pred[e]
+            s.local_pose = local_poses[e]
+        return local_poses.cpu().numpy()
+
+    def _mark_agent_batch(self, marks):
+        """``marks``: per active episode (local_map, m, footprint radius, (r0, r1, c0, c1), centres) -> one launch."""
+        E = len(marks)
+        lm0, m, rad = marks[0][0], marks[0][1], marks[0][2]
+        maps = (C.c_void_p * E)(*[mk[0].data_ptr() for mk in marks])
+        squares = (C.c_int * (4 * E))(*[int(v) for mk in marks for v in mk[3]])
+        n_centres = (C.c_int * E)(*[len(mk[4]) for mk in marks])
+        flat = [0] * (4 * E)
+        for e, mk in enumerate(marks):
+            for k, (cr, cc) in enumerate(mk[4]):
+                flat[4 * e + 2 * k], flat[4 * e + 2 * k + 1] = int(cr), int(cc)
+        centres = (C.c_int * (4 * E))(*flat)
+        with torch.cuda.device(self.device):
+            rc = _lib.load().peanut_map_mark_agent_batch(E, maps, int(lm0.shape[0]), m, squares, self.active[0]._selem_mask.data_ptr(),
+                                                         rad, n_centres, centres, _lib.current_stream_ptr(self.device))
+        _lib.check(rc, "peanut_map_mark_agent_batch")
+
+    def _predict_batch(self, crops):
+        """One prediction forward over the windows of the episodes that predict on this step -> [n,K,W,W]."""
+        return self.active[0].prediction_model.get_prediction_batch(torch.cat(crops))
+
+    # ---- host logic ----
+    def drop(self, state):
+        """Take an episode (the state or its index in ``active``) out of the batch."""
+        if isinstance(state, int):
+            del self.active[state]
+        else:
+            self.active.remove(state)
+
+    def reset_active(self):
+        self.active = list(self.states)
+
+    def _check_batch(self, obs, infos):
+        E = len(self.active)
+        if E == 0:
+            raise ValueError("no active episode")
+        if len(infos) != E:
+            raise ValueError(f"{len(infos)} infos for {E} active episodes")
+        if obs.shape[0] != E:
+            raise ValueError(f"obs holds {obs.shape[0]} frames for {E} active episodes")
+        return E
+
+    def init_with_obs(self, obs, infos):
+        """``Agent_State.init_with_obs`` for every active episode: obs [E,C,h,w], E infos."""
+        E = self._check_batch(obs, infos)
+        for s in self.active:
+            s.l_step = 0
+            s.step = 0
+        locs = self._map_step(obs, self._upload_poses([i['sensor_pose'] for i in infos]))
+        for e, s in enumerate(self.active):
+            s.locs = locs[e]
+            r, c = s.locs[1], s.locs[0]
+            loc_r, loc_c = [int(r * 100.0 / s.args.map_resolution), int(c * 100.0 / s.args.map_resolution)]
+            s.local_map[2:4, loc_r - 1:loc_r + 2, loc_c - 1:loc_c + 2] = 1.
+            rgoal = [0.1, 0.1]
+            s.global_goals = [[int(rgoal[0] * s.local_w), int(rgoal[1] * s.local_h)]]
+            s.global_goals = [[min(x, int(s.local_w - 1)), min(y, int(s.local_h - 1))] for x, y in s.global_goals]
+
+    def update_local_maps(self, obs, sensor_poses):
+        """``Agent_State.update_local_map`` for every active episode: one pose upload, one projection, one read-back, the
+        host decisions per episode, one marking launch."""
+        act = list(self.active)
+        locs = self._map_step(obs, self._upload_poses(sensor_poses))
+        marks, cells = [], []
+        for e, s in enumerate(act):
+            loc_r, loc_c, traj_rad, centres = s._local_map_host(locs[e])
+            marks.append(s._mark_args(loc_r, loc_c, traj_rad, centres) + (centres,))
+            cells.append((loc_r, loc_c))
+        self._mark_agent_batch(marks)
+        for s, (loc_r, loc_c) in zip(act, cells):
+            s.loc_r, s.loc_c = loc_r, loc_c
+
+    def update_state(self, obs, infos):
+        """``Agent_State.update_state`` for every active episode: obs [E,C,h,w], E infos.  Returns E flags: predicted."""
+        E = self._check_batch(obs, infos)
+        act = list(self.active)
+        for s, i in zip(act, infos):
+            s.goal_cat = i['goal_cat_id']
+        self.update_local_maps(obs, [i['sensor_pose'] for i in infos])
+        predicted = [False] * E
+        if not self.batch_predictions:
+            for e, s in enumerate(act):
+                s._step_full_map()
+                if s._prediction_due():
+                    select = getattr(s.args, "select_goal", True)
+                    s.update_prediction(goal_follows=select)
+                    if select:
+                        s.update_global_goal()
+                    predicted[e] = True
+                s.inc_step()
+            return predicted
+        for s in act:
+            s._step_full_map()
+        due = [e for e, s in enumerate(act) if s._prediction_due()]
+        if due:
+            crops = [act[e]._prediction_input(getattr(act[e].args, "select_goal", True)) for e in due]
+            preds = self._predict_batch(crops)
+            for k, e in enumerate(due):
+                act[e]._prediction_output(preds[k])
+                if getattr(act[e].args, "select_goal", True):
+                    act[e].update_global_goal()
+                predicted[e] = True
+        for s in act:
+            s.inc_step()
         return predicted

@@ -99,9 +99,9 @@ __device__ __forceinline__ bool stairs_branch(const StairStats& s) {
 // ---- 1. depth -> normalised coordinates (mapping.py:59-88) + stairs statistics ----
 // ---- 0. du_scale > 1 (mapping.py:60,80-82): depth sub-sampled [::s, ::s], semantic channels AvgPool2d(s) -> an observation
 //         of (h / s) x (w / s) points in the layout the other kernels read (RGB channels are not used by the mapping) ----
-__global__ __launch_bounds__(256) void map_decimate_kernel(const float* __restrict__ obs, float* __restrict__ dec, MapP P) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int ch = 3 + blockIdx.y;                       // depth, then the semantic channels
+__device__ __forceinline__ void map_decimate_body(int blk, int chan, const float* __restrict__ obs, float* __restrict__ dec, const MapP& P) {
+  const int p = blk * blockDim.x + threadIdx.x;
+  const int ch = 3 + chan;                             // depth, then the semantic channels
   if (p >= P.N) return;
   const int r = p / P.w, c = p - r * P.w;
   const float* src = obs + (size_t)ch * P.fh * P.fw;
@@ -116,13 +116,16 @@ __global__ __launch_bounds__(256) void map_decimate_kernel(const float* __restri
   }
   dec[(size_t)ch * P.N + p] = v;
 }
+__global__ __launch_bounds__(256) void map_decimate_kernel(const float* __restrict__ obs, float* __restrict__ dec, MapP P) {
+  map_decimate_body(blockIdx.x, blockIdx.y, obs, dec, P);
+}
 
-__global__ __launch_bounds__(256) void map_points_kernel(const float* __restrict__ obs, float* __restrict__ coords,
-                                                         StairStats* __restrict__ stats, MapP P) {
+__device__ __forceinline__ void map_points_body(int blk, const float* __restrict__ obs, float* __restrict__ coords,
+                                                StairStats* __restrict__ stats, const MapP& P) {
   __shared__ unsigned s_n, s_mid, s_le, s_max, s_min;
   if (threadIdx.x == 0) { s_n = 0; s_mid = 0; s_le = 0; s_max = 0u; s_min = 0xffffffffu; }
   __syncthreads();
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = blk * blockDim.x + threadIdx.x;
   if (p < P.N) {
     const int r = p / P.w, c = p - r * P.w;
     const float d = obs[3 * P.N + p];
@@ -155,13 +158,17 @@ __global__ __launch_bounds__(256) void map_points_kernel(const float* __restrict
     if (s_min != 0xffffffffu) atomicMin(&stats->min_gt, s_min);
   }
 }
+__global__ __launch_bounds__(256) void map_points_kernel(const float* __restrict__ obs, float* __restrict__ coords,
+                                                         StairStats* __restrict__ stats, MapP P) {
+  map_points_body(blockIdx.x, obs, coords, stats, P);
+}
 
 // ---- 3. splat position + base-cell key (depth_utils.py:217-236) ----
-__global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__ obs, const float* __restrict__ coords,
-                                                       const StairStats* __restrict__ stats, float* __restrict__ pos,
-                                                       unsigned* __restrict__ keys, int* __restrict__ cell_cnt,
-                                                       int* __restrict__ cell_first, MapP P) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_keys_body(int blk, const float* __restrict__ obs, const float* __restrict__ coords,
+                                              const StairStats* __restrict__ stats, float* __restrict__ pos,
+                                              unsigned* __restrict__ keys, int* __restrict__ cell_cnt,
+                                              int* __restrict__ cell_first, const MapP& P) {
+  const int p = blk * blockDim.x + threadIdx.x;
   if (p >= P.N) return;
   float xs = coords[p], ys = coords[P.N + p], zs = coords[2 * P.N + p];
   if (stairs_branch(*stats)) {
@@ -187,34 +194,49 @@ __global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__
     atomicMin(&cell_first[key], p);      // its first point: the one that will claim the segment
   }
 }
+__global__ __launch_bounds__(256) void map_keys_kernel(const float* __restrict__ obs, const float* __restrict__ coords,
+                                                       const StairStats* __restrict__ stats, float* __restrict__ pos,
+                                                       unsigned* __restrict__ keys, int* __restrict__ cell_cnt,
+                                                       int* __restrict__ cell_first, MapP P) {
+  map_keys_body(blockIdx.x, obs, coords, stats, pos, keys, cell_cnt, cell_first, P);
+}
 
 // ---- 3b. grouping by base cell, point order inside a cell (what a stable sort by cell would give) ----
 // The voxel replay needs every cell's points contiguous and in point order (CPU scatter_add_ adds them in that order,
 // and fp32 sums depend on it).  A sort would also order the CELLS, which nobody needs; so: count, claim, fill, rank.
-__global__ __launch_bounds__(256) void map_alloc_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_cnt,
-                                                        const int* __restrict__ cell_first, int* __restrict__ cell_head,
-                                                        int* __restrict__ cursor, int N) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_alloc_body(int blk, const unsigned* __restrict__ keys, const int* __restrict__ cell_cnt,
+                                               const int* __restrict__ cell_first, int* __restrict__ cell_head,
+                                               int* __restrict__ cursor, int N) {
+  const int p = blk * blockDim.x + threadIdx.x;
   if (p >= N) return;
   const unsigned k = keys[p];
   if (k != INVALID_KEY && cell_first[k] == p) cell_head[k] = atomicAdd(cursor, cell_cnt[k]);
 }
+__global__ __launch_bounds__(256) void map_alloc_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_cnt,
+                                                        const int* __restrict__ cell_first, int* __restrict__ cell_head,
+                                                        int* __restrict__ cursor, int N) {
+  map_alloc_body(blockIdx.x, keys, cell_cnt, cell_first, cell_head, cursor, N);
+}
 
-__global__ __launch_bounds__(256) void map_fill_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
-                                                       int* __restrict__ cell_fill, unsigned* __restrict__ seg, int N) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_fill_body(int blk, const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
+                                              int* __restrict__ cell_fill, unsigned* __restrict__ seg, int N) {
+  const int p = blk * blockDim.x + threadIdx.x;
   if (p >= N) return;
   const unsigned k = keys[p];
   if (k != INVALID_KEY) seg[cell_head[k] + atomicAdd(&cell_fill[k], 1)] = (unsigned)p;    // arrival order
 }
+__global__ __launch_bounds__(256) void map_fill_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
+                                                       int* __restrict__ cell_fill, unsigned* __restrict__ seg, int N) {
+  map_fill_body(blockIdx.x, keys, cell_head, cell_fill, seg, N);
+}
 
-__global__ __launch_bounds__(256) void map_place_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
-                                                        const int* __restrict__ cell_cnt, const unsigned* __restrict__ seg,
-                                                        const int* __restrict__ cursor, const float* __restrict__ obs,
-                                                        const float* __restrict__ pos, unsigned* __restrict__ skey,
-                                                        unsigned* __restrict__ sidx, float* __restrict__ wts6,
-                                                        float* __restrict__ feat_s, MapP P) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_place_body(int blk, const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
+                                               const int* __restrict__ cell_cnt, const unsigned* __restrict__ seg,
+                                               const int* __restrict__ cursor, const float* __restrict__ obs,
+                                               const float* __restrict__ pos, unsigned* __restrict__ skey,
+                                               unsigned* __restrict__ sidx, float* __restrict__ wts6,
+                                               float* __restrict__ feat_s, const MapP& P) {
+  const int p = blk * blockDim.x + threadIdx.x;
   if (p >= P.N) return;
   if (p >= *cursor) skey[p] = INVALID_KEY;           // the tail behind the last segment holds no point
   const unsigned k = keys[p];
@@ -238,6 +260,14 @@ __global__ __launch_bounds__(256) void map_place_kernel(const unsigned* __restri
   wts6[5 * P.N + j] = 1.0f - fabsf(p2 - (g2 + 1.0f));
   for (int f = 1; f < P.F; ++f) feat_s[(f - 1) * P.N + j] = obs[(3 + f) * P.N + p];
 }
+__global__ __launch_bounds__(256) void map_place_kernel(const unsigned* __restrict__ keys, const int* __restrict__ cell_head,
+                                                        const int* __restrict__ cell_cnt, const unsigned* __restrict__ seg,
+                                                        const int* __restrict__ cursor, const float* __restrict__ obs,
+                                                        const float* __restrict__ pos, unsigned* __restrict__ skey,
+                                                        unsigned* __restrict__ sidx, float* __restrict__ wts6,
+                                                        float* __restrict__ feat_s, MapP P) {
+  map_place_body(blockIdx.x, keys, cell_head, cell_cnt, seg, cursor, obs, pos, skey, sidx, wts6, feat_s, P);
+}
 
 // ---- 4. re-arm the per-cell tables for the next frame (only the touched entries) ----
 __device__ __forceinline__ void map_rearm(int p, const unsigned* __restrict__ keys, int* __restrict__ cell_head,
@@ -251,11 +281,11 @@ __device__ __forceinline__ void map_rearm(int p, const unsigned* __restrict__ ke
 }
 
 // ---- 5. per-voxel replay of the 8 corner passes ----
-__global__ __launch_bounds__(256) void map_voxels_kernel(const float* __restrict__ wts6, const float* __restrict__ feat_s,
-                                                         const unsigned* __restrict__ skey,
-                                                         const int* __restrict__ cell_head, const int* __restrict__ cell_cnt,
-                                                         float* __restrict__ proj, MapP P) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_voxels_body(int blk, const float* __restrict__ wts6, const float* __restrict__ feat_s,
+                                                const unsigned* __restrict__ skey,
+                                                const int* __restrict__ cell_head, const int* __restrict__ cell_cnt,
+                                                float* __restrict__ proj, const MapP& P) {
+  const long long t = (long long)blk * blockDim.x + threadIdx.x;
   const long long total = (long long)P.N * 8 * P.F;
   if (t >= total) return;
   const int f = (int)(t % P.F);
@@ -314,6 +344,12 @@ __global__ __launch_bounds__(256) void map_voxels_kernel(const float* __restrict
     atomicAdd(&proj[o], val);                                                   // all_height_proj
     if (v2 >= P.min_z && v2 < P.max_z) atomicAdd(&proj[P.F * P.vr * P.vr + o], val);   // agent_height_proj
   }
+}
+__global__ __launch_bounds__(256) void map_voxels_kernel(const float* __restrict__ wts6, const float* __restrict__ feat_s,
+                                                         const unsigned* __restrict__ skey,
+                                                         const int* __restrict__ cell_head, const int* __restrict__ cell_cnt,
+                                                         float* __restrict__ proj, MapP P) {
+  map_voxels_body(blockIdx.x, wts6, feat_s, skey, cell_head, cell_cnt, proj, P);
 }
 
 // ---- 6. thresholds -> egocentric window, fp_map_pred; clears the projections for the next frame ----
@@ -439,10 +475,10 @@ __device__ __forceinline__ TapAddr tap_addr(const Tap& rt, bool in_img, const Ma
   return a;
 }
 
-__global__ __launch_bounds__(256) void map_warp_kernel(const float* __restrict__ view, const float* __restrict__ maps_last,
-                                                       float* __restrict__ map_pred, const WarpT* __restrict__ wtp,
-                                                       MapP P) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void map_warp_body(int blk, const float* __restrict__ view, const float* __restrict__ maps_last,
+                                              float* __restrict__ map_pred, const WarpT* __restrict__ wtp,
+                                              const MapP& P) {
+  const int t = blk * blockDim.x + threadIdx.x;
   const int M = P.M;
   if (t >= M * M) return;
   const int y = t / M, x = t - y * M;
@@ -517,6 +553,11 @@ __global__ __launch_bounds__(256) void map_warp_kernel(const float* __restrict__
     map_pred[(size_t)c * plane + t] = fmaxf(last, tr);     // torch.max over the stacked pair (mapping.py:175-177)
   }
 }
+__global__ __launch_bounds__(256) void map_warp_kernel(const float* __restrict__ view, const float* __restrict__ maps_last,
+                                                       float* __restrict__ map_pred, const WarpT* __restrict__ wtp,
+                                                       MapP P) {
+  map_warp_body(blockIdx.x, view, maps_last, map_pred, wtp, P);
+}
 
 
 // ---- Agent_State.update_local_map's bookkeeping after the projection (nav/agent/agent_state.py:281-296), one launch ----
@@ -535,8 +576,9 @@ __device__ __forceinline__ bool stamp_hits(int r, int c, int cr, int cc, int m, 
   if (cc + dc >= 0 ? (cc + dc != c) : (cc + dc + m != c)) return false;
   return selem[(dr + rad) * (2 * rad + 1) + (dc + rad)] != 0;
 }
-__global__ __launch_bounds__(256) void map_mark_agent_kernel(float* __restrict__ local_map, const unsigned char* __restrict__ selem, MarkP p) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void map_mark_agent_body(int blk, float* __restrict__ local_map, const unsigned char* __restrict__ selem,
+                                                    const MarkP& p) {
+  const int i = blk * 256 + threadIdx.x;
   if (i >= p.m * p.m) return;
   const int r = i / p.m, c = i - r * p.m;
   const size_t plane = (size_t)p.m * p.m;
@@ -546,6 +588,101 @@ __global__ __launch_bounds__(256) void map_mark_agent_kernel(float* __restrict__
   bool hit = false;
   for (int k = 0; k < p.n_centres; ++k) hit = hit || stamp_hits(r, c, p.cr[k], p.cc[k], p.m, p.rad, selem);
   if (hit) local_map[plane + i] = 1.0f;
+}
+__global__ __launch_bounds__(256) void map_mark_agent_kernel(float* __restrict__ local_map, const unsigned char* __restrict__ selem, MarkP p) {
+  map_mark_agent_body(blockIdx.x, local_map, selem, p);
+}
+
+// ---- the batched step: E independent episodes, the episode on the grid's last dimension ----
+// Every kernel below is the body of its single-episode counterpart applied to episode slot e's scratch: same code, same
+// order, so an episode's outputs are bit-identical to peanut_map_forward's.  The scratch of the batched call is its own
+// allocation (peanut_map_reserve), [max_batch] copies of every array the handle owns for the single step, so a single
+// step between two batched ones touches none of it.
+struct MapScratch {
+  float *coords, *pos;
+  unsigned *keys, *seg, *skeys, *sidx;
+  int *cell_head, *cell_cnt, *cell_first, *cell_fill, *cursor;
+  StairStats* stats;
+  float *wts6, *feat_s, *proj, *view, *obs_dec;
+  WarpT* wt;
+};
+struct MapBatchArgs {
+  MapScratch S;                                   // slot 0 of every array; slot e lies e strides further (map_slot)
+  const float* obs;                               // [E][C][fh][fw]
+  const float* pts;                               // the observation the point kernels read, [E][C][N]: obs, or S.obs_dec at du_scale > 1
+  const float* pose_obs;                          // [E][3]
+  float* poses;                                   // [E][3]
+  float* fp_map_pred;                             // [E][V][V]
+  const float* maps_last[PEANUT_MAP_MAX_BATCH];   // by value: every episode owns its map tensors
+  float* map_pred[PEANUT_MAP_MAX_BATCH];
+};
+__device__ __forceinline__ MapScratch map_slot(const MapScratch& S, int e, const MapP& P) {
+  const size_t N = (size_t)P.N, cells = (size_t)P.vr * P.vr, vox = cells * P.zb, se = (size_t)e;
+  MapScratch s;
+  s.coords = S.coords + se * 3 * N; s.pos = S.pos + se * 3 * N;
+  s.keys = S.keys + se * N; s.seg = S.seg + se * N; s.skeys = S.skeys + se * N; s.sidx = S.sidx + se * N;
+  s.cell_head = S.cell_head + se * vox; s.cell_cnt = S.cell_cnt + se * vox; s.cell_first = S.cell_first + se * vox;
+  s.cell_fill = S.cell_fill + se * vox; s.cursor = S.cursor + se; s.stats = S.stats + se;
+  s.wts6 = S.wts6 + se * 6 * N; s.feat_s = S.feat_s + se * P.ncat * N; s.proj = S.proj + se * 2 * P.F * cells;
+  s.view = S.view + se * P.C * cells; s.obs_dec = S.obs_dec ? S.obs_dec + se * P.C * N : nullptr; s.wt = S.wt + se;
+  return s;
+}
+__device__ __forceinline__ const float* map_pts(const MapBatchArgs& A, int e, const MapP& P) { return A.pts + (size_t)e * P.C * P.N; }
+
+__global__ __launch_bounds__(256) void map_decimate_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.z;
+  map_decimate_body(blockIdx.x, blockIdx.y, A.obs + (size_t)e * P.C * P.fh * P.fw, map_slot(A.S, e, P).obs_dec, P);
+}
+__global__ __launch_bounds__(256) void map_points_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.y;
+  const MapScratch s = map_slot(A.S, e, P);
+  map_points_body(blockIdx.x, map_pts(A, e, P), s.coords, s.stats, P);
+}
+__global__ __launch_bounds__(256) void map_keys_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.y;
+  const MapScratch s = map_slot(A.S, e, P);
+  map_keys_body(blockIdx.x, map_pts(A, e, P), s.coords, s.stats, s.pos, s.keys, s.cell_cnt, s.cell_first, P);
+}
+__global__ __launch_bounds__(256) void map_alloc_batch_kernel(const MapBatchArgs A, MapP P) {
+  const MapScratch s = map_slot(A.S, blockIdx.y, P);
+  map_alloc_body(blockIdx.x, s.keys, s.cell_cnt, s.cell_first, s.cell_head, s.cursor, P.N);
+}
+__global__ __launch_bounds__(256) void map_fill_batch_kernel(const MapBatchArgs A, MapP P) {
+  const MapScratch s = map_slot(A.S, blockIdx.y, P);
+  map_fill_body(blockIdx.x, s.keys, s.cell_head, s.cell_fill, s.seg, P.N);
+}
+__global__ __launch_bounds__(256) void map_place_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.y;
+  const MapScratch s = map_slot(A.S, e, P);
+  map_place_body(blockIdx.x, s.keys, s.cell_head, s.cell_cnt, s.seg, s.cursor, map_pts(A, e, P), s.pos, s.skeys, s.sidx, s.wts6,
+                 s.feat_s, P);
+}
+__global__ __launch_bounds__(256) void map_voxels_batch_kernel(const MapBatchArgs A, MapP P) {
+  const MapScratch s = map_slot(A.S, blockIdx.y, P);
+  map_voxels_body(blockIdx.x, s.wts6, s.feat_s, s.skeys, s.cell_head, s.cell_cnt, s.proj, P);
+}
+// (the re-arming covers every slot the call used: one grid row per episode)
+__global__ __launch_bounds__(256) PEANUT_NO_PK_F32 void map_finish_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.y;
+  const MapScratch s = map_slot(A.S, e, P);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0) map_pose(A.pose_obs + 3 * e, A.poses + 3 * e, s.wt, P);
+  map_view(t, s.proj, s.view, A.fp_map_pred + (size_t)e * P.vr * P.vr, s.stats, P);
+  map_rearm(t, s.keys, s.cell_head, s.cell_cnt, s.cell_first, s.cell_fill, s.cursor, P.N);
+}
+__global__ __launch_bounds__(256) void map_warp_batch_kernel(const MapBatchArgs A, MapP P) {
+  const int e = blockIdx.y;
+  const MapScratch s = map_slot(A.S, e, P);
+  map_warp_body(blockIdx.x, s.view, A.maps_last[e], A.map_pred[e], s.wt, P);
+}
+
+struct MarkBatchArgs {
+  float* maps[PEANUT_MAP_MAX_BATCH];
+  MarkP p[PEANUT_MAP_MAX_BATCH];
+};
+__global__ __launch_bounds__(256) void map_mark_agent_batch_kernel(const MarkBatchArgs A, const unsigned char* __restrict__ selem) {
+  const int e = blockIdx.y;
+  map_mark_agent_body(blockIdx.x, A.maps[e], selem, A.p[e]);
 }
 }  // namespace
 }  // namespace peanut
@@ -569,8 +706,21 @@ struct peanut_map {
   WarpT* wt = nullptr;
   bool use_graph = false;    // peanut_map_use_graph: the launches of a step replayed as one hipGraph
   GraphCache graphs;
+  MapScratch batch{};        // peanut_map_reserve: [reserved] slots of everything above, for peanut_map_forward_batch
+  int reserved = 0;
+  int last_launches = 0;     // peanut_map_debug_launches
+  void free_batch() {
+    for (void* p : {(void*)batch.coords, (void*)batch.pos, (void*)batch.keys, (void*)batch.seg, (void*)batch.skeys, (void*)batch.sidx,
+                    (void*)batch.cell_head, (void*)batch.cell_cnt, (void*)batch.cell_first, (void*)batch.cell_fill, (void*)batch.cursor,
+                    (void*)batch.stats, (void*)batch.wts6, (void*)batch.feat_s, (void*)batch.proj, (void*)batch.view,
+                    (void*)batch.obs_dec, (void*)batch.wt})
+      if (p) (void)hipFree(p);
+    batch = MapScratch{};
+    reserved = 0;
+  }
   ~peanut_map() {
     graphs.clear();
+    free_batch();
     for (void* p : {(void*)coords, (void*)pos, (void*)keys, (void*)seg, (void*)skeys, (void*)sidx, (void*)cell_head,
                     (void*)cell_cnt, (void*)cell_first, (void*)cell_fill, (void*)cursor,
                     (void*)stats, (void*)wts6, (void*)feat_s, (void*)proj, (void*)view, (void*)obs_dec, (void*)wt})
@@ -677,25 +827,27 @@ int peanut_map_forward(peanut_map_t* h, const float* obs, const float* pose_obs,
     const MapP& P = h->P;
     const int nb = (P.N + 255) / 256;
     const float* obs = obs_full;
+    int n = 0;                                   // launches enqueued (peanut_map_debug_launches)
     if (P.du > 1) {
-      hipLaunchKernelGGL(map_decimate_kernel, dim3(nb, 1 + P.ncat), dim3(256), 0, s, obs_full, h->obs_dec, P);
+      hipLaunchKernelGGL(map_decimate_kernel, dim3(nb, 1 + P.ncat), dim3(256), 0, s, obs_full, h->obs_dec, P); ++n;
       obs = h->obs_dec;
     }
-    hipLaunchKernelGGL(map_points_kernel, dim3(nb), dim3(256), 0, s, obs, h->coords, h->stats, P);
+    hipLaunchKernelGGL(map_points_kernel, dim3(nb), dim3(256), 0, s, obs, h->coords, h->stats, P); ++n;
     hipLaunchKernelGGL(map_keys_kernel, dim3(nb), dim3(256), 0, s, obs, h->coords, h->stats, h->pos, h->keys, h->cell_cnt,
-                       h->cell_first, P);
-    hipLaunchKernelGGL(map_alloc_kernel, dim3(nb), dim3(256), 0, s, h->keys, h->cell_cnt, h->cell_first, h->cell_head, h->cursor, P.N);
-    hipLaunchKernelGGL(map_fill_kernel, dim3(nb), dim3(256), 0, s, h->keys, h->cell_head, h->cell_fill, h->seg, P.N);
+                       h->cell_first, P); ++n;
+    hipLaunchKernelGGL(map_alloc_kernel, dim3(nb), dim3(256), 0, s, h->keys, h->cell_cnt, h->cell_first, h->cell_head, h->cursor, P.N); ++n;
+    hipLaunchKernelGGL(map_fill_kernel, dim3(nb), dim3(256), 0, s, h->keys, h->cell_head, h->cell_fill, h->seg, P.N); ++n;
     hipLaunchKernelGGL(map_place_kernel, dim3(nb), dim3(256), 0, s, h->keys, h->cell_head, h->cell_cnt, h->seg, h->cursor, obs, h->pos,
-                       h->skeys, h->sidx, h->wts6, h->feat_s, P);
+                       h->skeys, h->sidx, h->wts6, h->feat_s, P); ++n;
     const long long vt = (long long)P.N * 8 * P.F;
     hipLaunchKernelGGL(map_voxels_kernel, dim3((unsigned)((vt + 255) / 256)), dim3(256), 0, s, h->wts6, h->feat_s, h->skeys,
-                       h->cell_head, h->cell_cnt, h->proj, P);
+                       h->cell_head, h->cell_cnt, h->proj, P); ++n;
     const int nfin = (std::max(P.vr * P.vr, P.N) + 255) / 256;
     hipLaunchKernelGGL(map_finish_kernel, dim3(nfin), dim3(256), 0, s, h->proj, h->view, fp_map_pred, h->stats, pose_obs, poses_inout,
-                       h->wt, h->keys, h->cell_head, h->cell_cnt, h->cell_first, h->cell_fill, h->cursor, P);
+                       h->wt, h->keys, h->cell_head, h->cell_cnt, h->cell_first, h->cell_fill, h->cursor, P); ++n;
     hipLaunchKernelGGL(map_warp_kernel, dim3((P.M * P.M + 255) / 256), dim3(256), 0, s, h->view, maps_last, map_pred,
-                       h->wt, P);
+                       h->wt, P); ++n;
+    h->last_launches = n;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(PEANUT_EHIP, std::string("peanut_map_forward: ") + hipGetErrorString(e));
     return 0;
@@ -705,13 +857,15 @@ int peanut_map_forward(peanut_map_t* h, const float* obs, const float* pose_obs,
                         (uintptr_t)fp_map_pred, (uintptr_t)map_pred, (uintptr_t)s}, s, enqueue);
 }
 
-int peanut_map_mark_agent(float* local_map, int channels, int m, int r0, int r1, int c0, int c1, const uint8_t* selem, int selem_radius,
-                          int n_centres, const int* centres_rc, void* stream) {
+// the argument checks of peanut_map_mark_agent for one map (shared with the batched call, which applies them to every episode
+// before anything is enqueued)
+static int mark_params(MarkP& p, const float* local_map, int channels, int m, int r0, int r1, int c0, int c1, const uint8_t* selem,
+                       int selem_radius, int n_centres, const int* centres_rc) {
   if (!local_map || !selem || (n_centres > 0 && !centres_rc)) return fail(PEANUT_EINVAL, "peanut_map_mark_agent: null argument");
   if (channels < 4 || m < 1 || selem_radius < 0 || 2 * selem_radius + 1 > m || n_centres < 0 || n_centres > 2)
     return fail(PEANUT_EINVAL, "peanut_map_mark_agent: bad dimensions");
   if (r0 < 0 || c0 < 0 || r1 > m || c1 > m) return fail(PEANUT_EINVAL, "peanut_map_mark_agent: the trajectory square is not a normalised slice");
-  MarkP p{m, r0, r1, c0, c1, selem_radius, n_centres, {0, 0}, {0, 0}};
+  p = MarkP{m, r0, r1, c0, c1, selem_radius, n_centres, {0, 0}, {0, 0}};
   for (int k = 0; k < n_centres; ++k) {
     const int cr = centres_rc[2 * k], cc = centres_rc[2 * k + 1];
     // the footprint's index range must be one torch accepts: [-m, m)
@@ -719,10 +873,124 @@ int peanut_map_mark_agent(float* local_map, int channels, int m, int r0, int r1,
       return fail(PEANUT_EINVAL, "peanut_map_mark_agent: footprint index out of range");
     p.cr[k] = cr; p.cc[k] = cc;
   }
+  return 0;
+}
+
+int peanut_map_mark_agent(float* local_map, int channels, int m, int r0, int r1, int c0, int c1, const uint8_t* selem, int selem_radius,
+                          int n_centres, const int* centres_rc, void* stream) {
+  MarkP p;
+  if (int rc = mark_params(p, local_map, channels, m, r0, r1, c0, c1, selem, selem_radius, n_centres, centres_rc)) return rc;
   hipLaunchKernelGGL(map_mark_agent_kernel, dim3((m * m + 255) / 256), dim3(256), 0, (hipStream_t)stream, local_map, selem, p);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("peanut_map_mark_agent: ") + hipGetErrorString(e));
 }
+
+int peanut_map_mark_agent_batch(int E, float* const* local_maps, int channels, int m, const int* squares, const uint8_t* selem,
+                                int selem_radius, const int* n_centres, const int* centres_rc, void* stream) {
+  if (E < 1 || E > PEANUT_MAP_MAX_BATCH) return fail(PEANUT_EINVAL, "peanut_map_mark_agent_batch: E must be 1..PEANUT_MAP_MAX_BATCH");
+  if (!local_maps || !squares || !n_centres || !centres_rc) return fail(PEANUT_EINVAL, "peanut_map_mark_agent_batch: null argument");
+  MarkBatchArgs A{};
+  for (int e = 0; e < E; ++e) {
+    const int* sq = squares + 4 * e;
+    if (int rc = mark_params(A.p[e], local_maps[e], channels, m, sq[0], sq[1], sq[2], sq[3], selem, selem_radius, n_centres[e],
+                             centres_rc + 4 * e))
+      return rc;
+    for (int o = 0; o < e; ++o)
+      if (local_maps[o] == local_maps[e]) return fail(PEANUT_EINVAL, "peanut_map_mark_agent_batch: two episodes share one map");
+    A.maps[e] = local_maps[e];
+  }
+  hipLaunchKernelGGL(map_mark_agent_batch_kernel, dim3((m * m + 255) / 256, E), dim3(256), 0, (hipStream_t)stream, A, selem);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("peanut_map_mark_agent_batch: ") + hipGetErrorString(e));
+}
+
+int peanut_map_reserve(peanut_map_t* h, int max_batch) {
+  if (!h) return fail(PEANUT_EINVAL, "peanut_map_reserve: null handle");
+  if (max_batch < 1 || max_batch > PEANUT_MAP_MAX_BATCH)
+    return fail(PEANUT_EINVAL, "peanut_map_reserve: max_batch must be 1..PEANUT_MAP_MAX_BATCH");
+  if (max_batch <= h->reserved) return 0;
+  PEANUT_HIP_CHECK(hipDeviceSynchronize());        // a batched step still in flight owns the slots about to be freed
+  h->free_batch();
+  const MapP& P = h->P;
+  MapScratch& b = h->batch;
+  const size_t E = (size_t)max_batch, N = P.N, cells = (size_t)P.vr * P.vr, vox = cells * P.zb;
+  // every array as peanut_map_create makes it, E times over, with the same initial contents
+  PEANUT_HIP_CHECK(hipMalloc(&b.coords, E * 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.pos, E * 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.keys, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.seg, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.skeys, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.sidx, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.cell_head, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMemset(b.cell_head, 0xff, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.cell_cnt, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMemset(b.cell_cnt, 0, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.cell_fill, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMemset(b.cell_fill, 0, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.cell_first, E * vox * sizeof(int)));
+  {
+    std::vector<int> big(E * vox, 0x7fffffff);
+    PEANUT_HIP_CHECK(hipMemcpy(b.cell_first, big.data(), big.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  PEANUT_HIP_CHECK(hipMalloc(&b.cursor, E * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMemset(b.cursor, 0, E * sizeof(int)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.stats, E * sizeof(StairStats)));
+  {
+    std::vector<StairStats> init(E, StairStats{0u, 0u, 0u, 0u, 0xffffffffu});
+    PEANUT_HIP_CHECK(hipMemcpy(b.stats, init.data(), E * sizeof(StairStats), hipMemcpyHostToDevice));
+  }
+  PEANUT_HIP_CHECK(hipMalloc(&b.wts6, E * 6 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.feat_s, E * P.ncat * N * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.proj, E * 2 * P.F * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMemset(b.proj, 0, E * 2 * P.F * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.view, E * P.C * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(hipMalloc(&b.wt, E * sizeof(WarpT)));
+  if (P.du > 1) PEANUT_HIP_CHECK(hipMalloc(&b.obs_dec, E * P.C * N * sizeof(float)));
+  PEANUT_HIP_CHECK(hipDeviceSynchronize());
+  h->reserved = max_batch;
+  return 0;
+}
+
+int peanut_map_forward_batch(peanut_map_t* h, int E, const float* obs, const float* pose_obs, const float* const* maps_last,
+                             float* poses_inout, float* fp_map_pred, float* const* map_pred, void* stream) {
+  if (!h || !obs || !pose_obs || !maps_last || !poses_inout || !fp_map_pred || !map_pred)
+    return fail(PEANUT_EINVAL, "peanut_map_forward_batch: null argument");
+  if (E < 1 || E > h->reserved)
+    return fail(PEANUT_EINVAL, "peanut_map_forward_batch: E must be 1..the batch peanut_map_reserve was given");
+  for (int e = 0; e < E; ++e) {
+    if (!maps_last[e] || !map_pred[e]) return fail(PEANUT_EINVAL, "peanut_map_forward_batch: null map pointer");
+    for (int o = 0; o < E; ++o)
+      if (maps_last[o] == map_pred[e]) return fail(PEANUT_EINVAL, "peanut_map_forward_batch: a map_pred must not alias a maps_last");
+    for (int o = 0; o < e; ++o)
+      if (map_pred[o] == map_pred[e]) return fail(PEANUT_EINVAL, "peanut_map_forward_batch: two episodes share one map_pred");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const MapP& P = h->P;
+  MapBatchArgs A{};
+  A.S = h->batch;
+  A.obs = obs; A.pts = P.du > 1 ? h->batch.obs_dec : obs;
+  A.pose_obs = pose_obs; A.poses = poses_inout; A.fp_map_pred = fp_map_pred;
+  for (int e = 0; e < E; ++e) { A.maps_last[e] = maps_last[e]; A.map_pred[e] = map_pred[e]; }
+  const int nb = (P.N + 255) / 256;
+  int n = 0;
+  if (P.du > 1) { hipLaunchKernelGGL(map_decimate_batch_kernel, dim3(nb, 1 + P.ncat, E), dim3(256), 0, s, A, P); ++n; }
+  hipLaunchKernelGGL(map_points_batch_kernel, dim3(nb, E), dim3(256), 0, s, A, P); ++n;
+  hipLaunchKernelGGL(map_keys_batch_kernel, dim3(nb, E), dim3(256), 0, s, A, P); ++n;
+  hipLaunchKernelGGL(map_alloc_batch_kernel, dim3(nb, E), dim3(256), 0, s, A, P); ++n;
+  hipLaunchKernelGGL(map_fill_batch_kernel, dim3(nb, E), dim3(256), 0, s, A, P); ++n;
+  hipLaunchKernelGGL(map_place_batch_kernel, dim3(nb, E), dim3(256), 0, s, A, P); ++n;
+  const long long vt = (long long)P.N * 8 * P.F;
+  hipLaunchKernelGGL(map_voxels_batch_kernel, dim3((unsigned)((vt + 255) / 256), E), dim3(256), 0, s, A, P); ++n;
+  const int nfin = (std::max(P.vr * P.vr, P.N) + 255) / 256;
+  hipLaunchKernelGGL(map_finish_batch_kernel, dim3(nfin, E), dim3(256), 0, s, A, P); ++n;
+  hipLaunchKernelGGL(map_warp_batch_kernel, dim3((P.M * P.M + 255) / 256, E), dim3(256), 0, s, A, P); ++n;
+  h->last_launches = n;
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(PEANUT_EHIP, std::string("peanut_map_forward_batch: ") + hipGetErrorString(e));
+  return 0;
+}
+
+int peanut_map_debug_launches(peanut_map_t* h) { return h ? h->last_launches : -1; }
 
 int peanut_map_use_graph(peanut_map_t* h, int enable) {
   if (!h) return fail(PEANUT_EINVAL, "null handle");

@@ -11,13 +11,12 @@
 
 namespace peanut {
 
-__global__ __launch_bounds__(128) void preprocess_obs_kernel(const uint8_t* __restrict__ rgb,
-                                                             const float* __restrict__ depth,
-                                                             const float* __restrict__ sem, int H, int W, int ncat,
-                                                             int ds, float base_cm, float span, float* __restrict__ obs) {
+__device__ __forceinline__ void preprocess_obs_body(int j, const uint8_t* __restrict__ rgb, const float* __restrict__ depth,
+                                                    const float* __restrict__ sem, int H, int W, int ncat,
+                                                    int ds, float base_cm, float span, float* __restrict__ obs) {
   __shared__ int s_zero;
   __shared__ unsigned s_max;   // depth >= 0, so the raw bit pattern orders like the float
-  const int j = blockIdx.x;                 // output column
+  // j: output column
   const int i = ds / 2 + j * ds;            // source column
   const int h = H / ds, w = W / ds;
   if (threadIdx.x == 0) { s_zero = 0; s_max = 0u; }
@@ -54,6 +53,23 @@ __global__ __launch_bounds__(128) void preprocess_obs_kernel(const uint8_t* __re
   }
 }
 
+__global__ __launch_bounds__(128) void preprocess_obs_kernel(const uint8_t* __restrict__ rgb,
+                                                             const float* __restrict__ depth,
+                                                             const float* __restrict__ sem, int H, int W, int ncat,
+                                                             int ds, float base_cm, float span, float* __restrict__ obs) {
+  preprocess_obs_body(blockIdx.x, rgb, depth, sem, H, W, ncat, ds, base_cm, span, obs);
+}
+
+// E frames in one launch: the frame on blockIdx.y, the same body on that frame's planes
+__global__ __launch_bounds__(128) void preprocess_obs_batch_kernel(const uint8_t* __restrict__ rgb,
+                                                                   const float* __restrict__ depth,
+                                                                   const float* __restrict__ sem, int H, int W, int ncat,
+                                                                   int ds, float base_cm, float span, float* __restrict__ obs) {
+  const size_t e = blockIdx.y, px = (size_t)H * W;
+  preprocess_obs_body(blockIdx.x, rgb + e * px * 3, depth + e * px, sem + e * px * ncat, H, W, ncat, ds, base_cm, span,
+                      obs + e * (size_t)(4 + ncat) * (H / ds) * (W / ds));
+}
+
 }  // namespace peanut
 
 extern "C" int peanut_preprocess_obs(const uint8_t* rgb, const float* depth, const float* sem, int H, int W, int ncat,
@@ -68,4 +84,17 @@ extern "C" int peanut_preprocess_obs(const uint8_t* rgb, const float* depth, con
                      ds, base_cm, span, obs);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("preprocess_obs: ") + hipGetErrorString(e));
+}
+
+extern "C" int peanut_preprocess_obs_batch(const uint8_t* rgb, const float* depth, const float* sem, int E, int H, int W, int ncat,
+                                           int ds, double min_d, double max_d, float* obs, void* stream) {
+  using namespace peanut;
+  if (!rgb || !depth || !sem || !obs) return fail(PEANUT_EINVAL, "peanut_preprocess_obs_batch: null argument");
+  if (E < 1 || E > PEANUT_MAP_MAX_BATCH) return fail(PEANUT_EINVAL, "peanut_preprocess_obs_batch: E must be 1..PEANUT_MAP_MAX_BATCH");
+  if (ds < 1 || H % ds || W % ds || ncat < 1) return fail(PEANUT_EINVAL, "peanut_preprocess_obs_batch: bad geometry");
+  const float base_cm = (float)(min_d * 100.0), span = (float)(max_d - min_d);      // as peanut_preprocess_obs forms them
+  hipLaunchKernelGGL(preprocess_obs_batch_kernel, dim3(W / ds, E), dim3(128), 0, (hipStream_t)stream, rgb, depth, sem, H, W,
+                     ncat, ds, base_cm, span, obs);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("preprocess_obs_batch: ") + hipGetErrorString(e));
 }

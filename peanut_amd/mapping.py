@@ -91,3 +91,69 @@ class Semantic_Mapping(nn.Module):
                                               _lib.current_stream_ptr(obs.device))
         _lib.check(rc, "peanut_map_forward")
         return fp_map_pred, map_pred, poses_last, poses_last
+
+    # ---- several episodes per step ----
+    MAX_BATCH = 16      # PEANUT_MAP_MAX_BATCH
+
+    def reserve(self, max_batch: int):
+        """Allocate the scratch of ``forward_batch`` for up to ``max_batch`` episodes (``peanut_map_reserve``; synchronous, and
+        the only allocation of the batched path).  A smaller or equal reserve is kept."""
+        max_batch = int(max_batch)
+        if not 1 <= max_batch <= self.MAX_BATCH:
+            raise ValueError(f"max_batch must be 1..{self.MAX_BATCH}, got {max_batch}")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.peanut_map_reserve(self._h, max_batch), "peanut_map_reserve")
+        self.reserved = max(getattr(self, "reserved", 0), max_batch)
+
+    def debug_launches(self) -> int:
+        """Kernels enqueued by the last ``forward`` / ``forward_batch`` call of this module."""
+        return int(self._lib.peanut_map_debug_launches(self._h))
+
+    def forward_batch(self, obs, pose_obs, maps_last, poses_last, out=None):
+        """``forward`` for E independent episodes in the launches of one single-episode step::
+
+            fp_map_pred [E,V,V], [map_pred_e [C,M,M]], poses_last, poses_last
+                = sem_map_module.forward_batch(obs [E,C,h,w], pose_obs [E,3], [maps_last_e [C,M,M]], poses_last [E,3])
+
+        ``maps_last`` is a sequence of E tensors (every episode owns its map); ``poses_last`` is updated in place.  ``out`` =
+        (fp_map_pred [E,V,V], [map_pred_e]) are caller-owned outputs, none of which may be one of ``maps_last``.  Per episode
+        every output has the bits ``forward`` gives on the same inputs.  Needs ``reserve(E)`` (or more) first."""
+        Cc, M, V = self.channels, self.map_cells, self.vision_range
+        h, w = self.args.frame_height, self.args.frame_width
+        if obs.dim() != 4:
+            raise ValueError(f"obs must be [E,{Cc},{h},{w}], got {tuple(obs.shape)}")
+        E = int(obs.shape[0])
+        if not 1 <= E <= getattr(self, "reserved", 0):
+            raise ValueError(f"forward_batch: E = {E} episodes, reserve() holds {getattr(self, 'reserved', 0)}")
+        self._chk(obs, (E, Cc, h, w), "obs")
+        self._chk(pose_obs, (E, 3), "pose_obs")
+        self._chk(poses_last, (E, 3), "poses_last")
+        if not poses_last.is_contiguous():
+            raise ValueError("poses_last must be contiguous (it is updated in place)")
+        maps_last = list(maps_last)
+        if len(maps_last) != E:
+            raise ValueError(f"maps_last holds {len(maps_last)} maps for {E} episodes")
+        for e, m in enumerate(maps_last):
+            self._chk(m, (Cc, M, M), f"maps_last[{e}]")
+        obs, pose_obs = obs.contiguous(), pose_obs.contiguous()
+        maps_last = [m.contiguous() for m in maps_last]
+        if out is None:
+            fp_map_pred = torch.empty((E, V, V), dtype=torch.float32, device=obs.device)
+            map_pred = [torch.empty((Cc, M, M), dtype=torch.float32, device=obs.device) for _ in range(E)]
+        else:
+            fp_map_pred, map_pred = out
+            map_pred = list(map_pred)
+            self._chk(fp_map_pred, (E, V, V), "out[0]")
+            if len(map_pred) != E:
+                raise ValueError(f"out[1] holds {len(map_pred)} maps for {E} episodes")
+            for e, m in enumerate(map_pred):
+                self._chk(m, (Cc, M, M), f"out[1][{e}]")
+            if not (fp_map_pred.is_contiguous() and all(m.is_contiguous() for m in map_pred)):
+                raise ValueError("out buffers must be contiguous")
+        last_p = (C.c_void_p * E)(*[m.data_ptr() for m in maps_last])
+        pred_p = (C.c_void_p * E)(*[m.data_ptr() for m in map_pred])
+        with torch.cuda.device(obs.device):
+            rc = self._lib.peanut_map_forward_batch(self._h, E, obs.data_ptr(), pose_obs.data_ptr(), last_p, poses_last.data_ptr(),
+                                                    fp_map_pred.data_ptr(), pred_p, _lib.current_stream_ptr(obs.device))
+        _lib.check(rc, "peanut_map_forward_batch")
+        return fp_map_pred, map_pred, poses_last, poses_last

@@ -50,6 +50,76 @@ def run_episode(state: Agent_State, frames: Iterable[Dict], goal_cat: int,
     return n_pred
 
 
+def run_episodes(states, episodes, goal_cats, detector=None,
+                 on_step: Optional[Callable[[int, List[Agent_State], List[bool]], None]] = None,
+                 batch_predictions: bool = False) -> List[int]:
+    """``run_episode`` for E episodes in lock-step on one device (``Agent_State_Group``): ``states`` E ``Agent_State``
+    objects with equal mapping arguments, ``episodes`` E frame sequences in the formats of ``run_episode``, ``goal_cats`` E
+    goal categories.  Per step the frames of the episodes still running are formatted, projected and marked as one batch;
+    with a ``detector`` that has ``semantic``, they go through ONE ``detector.semantic(rgb[E].flip(-1), ..., goal_cats)``
+    call.  Episodes may differ in length: a finished one drops out and the others go on.  ``on_step(i, active_states,
+    predicted)`` is called after every step.  Returns the number of predictions per episode."""
+    import torch
+    from .agent_helper import preprocess_obs_batch
+    from .agent_state import Agent_State_Group
+    states, goal_cats = list(states), [int(g) for g in goal_cats]
+    iters = [iter(ep) for ep in episodes]
+    if not (len(states) == len(iters) == len(goal_cats)):
+        raise ValueError(f"{len(states)} states, {len(iters)} episodes and {len(goal_cats)} goal categories")
+    group = Agent_State_Group(states, batch_predictions=batch_predictions)
+    args = states[0].args
+    for s in states:
+        s.reset()
+    n_pred = [0] * len(states)
+    index = {id(s): e for e, s in enumerate(states)}
+    i = 0
+    while True:
+        frames = []
+        for s in list(group.active):
+            fr = next(iters[index[id(s)]], None)
+            if fr is None:
+                group.drop(s)                      # this episode is over; the others go on
+            else:
+                frames.append(fr)
+        if not group.active:
+            break
+        act = list(group.active)
+        goals = [goal_cats[index[id(s)]] for s in act]
+        if all("obs" in fr for fr in frames):
+            obs = torch.cat([fr["obs"] for fr in frames])
+        else:
+            if any("obs" in fr for fr in frames):
+                raise ValueError("the frames of one step mix ready observations and raw tuples")
+            raw = [fr for fr in frames if "masks" not in fr]
+            if raw and detector is None:
+                raise ValueError("frame carries no instance masks and no detector was given")
+            rgb = torch.stack([fr["rgb"] for fr in frames])
+            depth = torch.stack([fr["depth"] for fr in frames])
+            if len(raw) == len(frames) and hasattr(detector, "semantic"):      # detector + accumulation: one library call
+                sem = detector.semantic(rgb.flip(-1), args.num_sem_categories - 1, args.sem_pred_prob_thr, args.goal_thr,
+                                        goals)                                  # RGB -> BGR
+            else:
+                sems = []
+                for fr, goal in zip(frames, goals):
+                    if "masks" not in fr:
+                        fr = dict(fr)
+                        fr["masks"], fr["classes"], fr["scores"] = detector(fr["rgb"].flip(-1))
+                    sems.append(accumulate_instances(fr["masks"], fr["classes"], fr["scores"], args.num_sem_categories - 1,
+                                                     args.sem_pred_prob_thr, args.goal_thr, goal))
+                sem = torch.stack(sems)
+            obs = preprocess_obs_batch(rgb, depth, sem, args)
+        infos = [{"sensor_pose": fr["sensor_pose"], "goal_cat_id": goal} for fr, goal in zip(frames, goals)]
+        if i == 0:
+            group.init_with_obs(obs, infos)
+        predicted = group.update_state(obs, infos)
+        for s, p in zip(act, predicted):
+            n_pred[index[id(s)]] += int(p)
+        if on_step is not None:
+            on_step(i, act, predicted)
+        i += 1
+    return n_pred
+
+
 def run_recorded_episode(agent, episode, on_step: Optional[Callable[[int, Dict], None]] = None) -> int:
     """One pass of the reference's inner loop (nav/collect.py:44-59: ``hab_env.reset(); nav_agent.reset();
     while not episode_over: action = nav_agent.act(observations)``) over a recorded episode

@@ -54,8 +54,11 @@ class HipDetector:
         return self.batch(x.to(self.device)[None])[0]
 
     def semantic(self, img_bgr, n_cats: int, sem_pred_prob_thr: float, goal_thr: float, goal_cat=None) -> torch.Tensor:
-        """One frame straight to the per-category mask sums [H,W,n_cats+1] (``peanut_rcnn_semantic``)."""
+        """One frame straight to the per-category mask sums [H,W,n_cats+1] (``peanut_rcnn_semantic``); a batch [B,H,W,3] with
+        ``goal_cat`` a sequence of B categories (or None) gives [B,H,W,n_cats+1] from the same single library call."""
         x = torch.from_numpy(np.ascontiguousarray(img_bgr)) if isinstance(img_bgr, np.ndarray) else img_bgr
+        if x.dim() == 4:
+            return self.net.semantic(x.to(self.device), n_cats, sem_pred_prob_thr, goal_thr, None if goal_cat is None else list(goal_cat))
         return self.net.semantic(x.to(self.device)[None], n_cats, sem_pred_prob_thr, goal_thr, [goal_cat])[0]
 
 

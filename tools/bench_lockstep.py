@@ -1,0 +1,271 @@
+#!/usr/bin/env python3
+"""Several episodes per GPU in lock-step against the same episodes one after the other, for E = 1, 2, 4, 8, in ONE process,
+the two sides alternating (A B A B A B: three repeats each, the spread of the three goes into the record):
+
+  (a) stage 2 alone: E sequential `Agent_State.update_local_map` (forward + pose read-back + mark_agent each) against one
+      `Agent_State_Group.update_local_maps` (forward_batch + ONE read-back + mark_agent_batch), microseconds per step of
+      E episodes, wall clock between device synchronisations (both sides end every step on a read-back);
+  (b) the config-4 pipeline shape of tools/configs_bench.py (Mask R-CNN R-101-FPN in the loop, 40-frame synthetic episodes
+      of tools/bench_pipeline.py, 720 x 720 prediction + goal selection): E sequential `run_episode` calls against one
+      `run_episodes`, steps/s/GPU summed over the episodes.
+
+    python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace]
+
+writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
+of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
+import argparse
+import glob
+import json
+import os
+import sqlite3
+import subprocess
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+BATCHES = (1, 2, 4, 8)
+
+
+def _stage2_obs(E, dev, seed=0):
+    """E observations [E,14,120,160]: a slanted wall 1.5-4 m away with sensor noise, three semantic rectangles."""
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.zeros(E, 14, 120, 160)
+    for e in range(E):
+        wall = 150.0 + 250.0 * torch.rand(1, generator=g).item()
+        cols = torch.arange(160.0)[None, :] - 80.0
+        obs[e, 3] = (wall + 0.4 * cols).clamp(50.0, 495.0) + torch.rand((120, 160), generator=g)
+        for k in (1, 4, 6):
+            r0, c0 = int(torch.randint(10, 80, (1,), generator=g)), int(torch.randint(5, 120, (1,), generator=g))
+            obs[e, 4 + k, r0:r0 + 30, c0:c0 + 30] = 1.0
+    return obs.to(dev)
+
+
+def _spread(v):
+    v = sorted(v)
+    return {"median": round(v[len(v) // 2], 3), "min": round(v[0], 3), "max": round(v[-1], 3), "runs": [round(x, 3) for x in v]}
+
+
+def _stage2_sides(E, dev):
+    from peanut_amd.agent_state import Agent_State, Agent_State_Group, default_args
+    args = default_args(sem_gpu_id=dev.index)
+    seq = [Agent_State(args, prediction_model=None) for _ in range(E)]
+    lock = [Agent_State(args, prediction_model=None) for _ in range(E)]
+    for s in seq + lock:
+        s.reset()
+    grp = Agent_State_Group(lock)
+    obs = _stage2_obs(E, dev)
+    pose = [0.0, 0.0, 0.05]                                   # the agent turns on the spot: it stays inside its local map
+    each = [obs[e:e + 1] for e in range(E)]
+
+    def sequential(n):
+        for _ in range(n):
+            for s, o in zip(seq, each):
+                s.poses = s._upload_pose(pose)
+                s.update_local_map(o)
+
+    def batched(n):
+        for _ in range(n):
+            grp.update_local_maps(obs, [pose] * E)
+    return sequential, batched, (seq, lock, grp)
+
+
+def stage2(dev, steps=2000, repeats=3):
+    out = {}
+    for E in BATCHES:
+        sequential, batched, keep = _stage2_sides(E, dev)
+        sequential(20)
+        batched(20)
+        t = {"sequential": [], "batched": []}
+        for _ in range(repeats):
+            for name, fn in (("sequential", sequential), ("batched", batched)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(steps)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / steps * 1e6)
+        seq, lock, _ = keep
+        same = all(torch.equal(a.local_map, b.local_map) and torch.equal(a.local_pose, b.local_pose) for a, b in zip(seq, lock))
+        out[str(E)] = {"sequential_us_per_step": _spread(t["sequential"]), "batched_us_per_step": _spread(t["batched"]),
+                       "speedup_median": round(_spread(t["sequential"])["median"] / _spread(t["batched"])["median"], 3),
+                       "maps_and_poses_bit_identical": bool(same)}
+        print(f"stage 2, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
+        del keep
+    return out
+
+
+def forward_only(dev, steps=2000, repeats=3):
+    """`Semantic_Mapping.forward` alone (the figure README "Measured" records for the map projection step: device events around a
+    chain of steps, no read-back) and `forward_batch` alone at every E, alternating, microseconds per call."""
+    from peanut_amd.agent_state import default_args
+    from peanut_amd.mapping import Semantic_Mapping
+    args = default_args(sem_gpu_id=dev.index)
+    args.device = dev
+    sm = Semantic_Mapping(args)
+    sm.reserve(max(BATCHES))
+    M = sm.map_cells
+    obs = _stage2_obs(max(BATCHES), dev)
+    rel = torch.tensor([0.0, 0.0, 0.05], device=dev).repeat(max(BATCHES), 1).contiguous()
+    out = {}
+    for E in BATCHES:
+        bufs = [[torch.zeros(14, M, M, device=dev) for _ in range(E)] for _ in range(2)]
+        fp1, fpE = torch.empty(1, 100, 100, device=dev), torch.empty(E, 100, 100, device=dev)
+        poses = torch.tensor([12.0, 12.0, 0.0], device=dev).repeat(E, 1).contiguous()
+
+        def single(n):
+            for i in range(n):
+                a, b = bufs[i & 1], bufs[1 - (i & 1)]
+                for e in range(E):
+                    sm(obs[e:e + 1], rel[e], a[e], poses[e], None, out=(fp1, b[e]))
+
+        def batch(n):
+            for i in range(n):
+                sm.forward_batch(obs[:E], rel[:E], bufs[i & 1], poses, out=(fpE, bufs[1 - (i & 1)]))
+        single(20)
+        batch(20)
+        t = {"single": [], "batch": []}
+        for _ in range(repeats):
+            for name, fn in (("single", single), ("batch", batch)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn(steps)
+                e1.record()
+                torch.cuda.synchronize()
+                t[name].append(e0.elapsed_time(e1) / steps * 1e3)
+        out[str(E)] = {"E_single_forwards_us": _spread(t["single"]), "one_forward_batch_us": _spread(t["batch"])}
+        print(f"forward only, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
+    return out
+
+
+def pipeline(dev, frames=40, repeats=3):
+    import gc
+
+    from bench_pipeline import synth_episode
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episode, run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(BATCHES)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    seq = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    lock = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    out = {}
+    for E in BATCHES:
+        goals = [3] * E
+
+        def sequential():
+            return sum(run_episode(seq[e], eps[e], goal_cat=3, detector=det) for e in range(E))
+
+        def lockstep():
+            return sum(run_episodes(lock[:E], eps[:E], goals, detector=det))
+        run_episode(seq[0], eps[0][:12], goal_cat=3, detector=det)            # warm-up: plans and workspaces of both batch sizes
+        run_episodes(lock[:E], [ep[:12] for ep in eps[:E]], goals, detector=det)
+        gc.collect()
+        t = {"sequential": [], "lockstep": []}
+        preds = {}
+        for _ in range(repeats):
+            for name, fn in (("sequential", sequential), ("lockstep", lockstep)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                preds[name] = fn()
+                torch.cuda.synchronize()
+                t[name].append(E * frames / (time.perf_counter() - t0))
+        out[str(E)] = {"sequential_steps_per_s": _spread(t["sequential"]), "lockstep_steps_per_s": _spread(t["lockstep"]),
+                       "speedup_median": round(_spread(t["lockstep"])["median"] / _spread(t["sequential"])["median"], 3),
+                       "predictions": preds}
+        print(f"pipeline, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
+    return out
+
+
+def trace_child(dev, E=8, steps=50):
+    """What the profiler watches: warm-up, a pause, `steps` sequential steps of E episodes, a pause, `steps` batched steps."""
+    sequential, batched, keep = _stage2_sides(E, dev)
+    sequential(5)
+    batched(5)
+    for fn in (sequential, batched):
+        torch.cuda.synchronize()
+        time.sleep(0.3)                                            # a kernel-free pause in front of each timed part
+        fn(steps)
+    torch.cuda.synchronize()
+
+
+def _summarise_trace(db_path, E, steps):
+    db = sqlite3.connect(db_path)
+    rows = db.execute("select name, start, end from kernels order by start").fetchall()
+    # the two pauses are the two widest idle intervals of the trace: warm-up | sequential | batched
+    cuts = sorted(sorted(range(1, len(rows)), key=lambda i: rows[i][1] - rows[i - 1][2])[-2:])
+    parts = {"sequential": rows[cuts[0]:cuts[1]], "batched": rows[cuts[1]:]}
+    res = {}
+    for name, ks in parts.items():
+        mapk = [k for k in ks if "map_" in k[0]]
+        busy = sum(k[2] - k[1] for k in ks)
+        gaps = sum(max(ks[i][1] - ks[i - 1][2], 0) for i in range(1, len(ks)))
+        res[name] = {"steps": steps, "kernels_per_step": round(len(ks) / steps, 2),
+                     "stage2_kernels_per_step": round(len(mapk) / steps, 2),
+                     "kernel_us_per_step": round(busy / steps / 1e3, 2), "idle_gap_us_per_step": round(gaps / steps / 1e3, 2),
+                     "span_us_per_step": round((ks[-1][2] - ks[0][1]) / steps / 1e3, 2)}
+    res["note"] = (f"E = {E}; a step is E episodes; torch's own kernels (pose stack, copies) are in kernels_per_step, the library's "
+                   "map_* kernels alone in stage2_kernels_per_step; under the profiler every launch is slower, so the us here "
+                   "show the split between kernel time and gaps, not the rate")
+    return res
+
+
+def trace(out_dir, E=8, steps=50):
+    tdir = os.path.join(out_dir, "trace_tmp")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tdir, "--", sys.executable, os.path.abspath(__file__), "--trace-child"]
+    try:
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240, text=True)
+    except (OSError, subprocess.TimeoutExpired) as e:
+        return {"error": f"rocprofv3 did not run: {e}"}
+    dbs = glob.glob(os.path.join(tdir, "**", "*.db"), recursive=True)
+    if r.returncode != 0 or not dbs:
+        return {"error": f"rocprofv3 exit {r.returncode}, {len(dbs)} databases", "tail": r.stdout[-600:]}
+    res = _summarise_trace(dbs[0], E, steps)
+    import shutil
+    shutil.rmtree(tdir, ignore_errors=True)                       # the database stays out of the repository; the summary is the record
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lockstep"))
+    ap.add_argument("--no-pipeline", action="store_true")
+    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if a.trace_child:
+        trace_child(dev)
+        return
+    os.makedirs(a.out, exist_ok=True)
+    rec = {"device": torch.cuda.get_device_name(dev), "batches": list(BATCHES),
+           "method": "one process; per E the two sides alternate, three repeats each; spread = min / median / max of the three",
+           "forward_only": forward_only(dev), "stage2": stage2(dev)}
+    if not a.no_pipeline:
+        rec["pipeline"] = pipeline(dev)
+    if not a.no_trace:
+        rec["trace"] = trace(a.out)
+    with open(os.path.join(a.out, "lockstep.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
