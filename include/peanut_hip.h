@@ -545,6 +545,35 @@ int peanut_goal_select(peanut_goal_t* g, const float* full_obstacle, const uint8
                        const uint8_t* visited_vis, const int lmb[4], int loc_r, int loc_c, const float* target_pred,
                        double dist_weight_temperature, int map_resolution, int goal_rc_out[2], double stats_out[4],
                        double* dist_out, double* value_out, void* stream);
+/* Goal selection for the episodes of a lock-step group (ABI 17): update_global_goal (nav/agent/agent_state.py:376-415) of up to
+ * PEANUT_GOAL_MAX_BATCH episodes in the launches and host synchronisations of ONE solve -- a relaxation round of the batch is one
+ * launch over (tiles, E), a check is one read-back of the [E][rounds] counters and one synchronisation, the stages between are one
+ * launch each.  Every episode keeps its own handle (its field, its last weights, its round hints) and gets, bit for bit, what
+ * peanut_goal_select gives on that handle alone: it sees the rounds its own solve would run, with rounds that wake none of its
+ * tiles in between (csrc/goal.hip), so an episode may be selected in a batch on one step and alone on the next, in any mix.
+ * E = 1 equals the single call.  Refused with PEANUT_EINVAL and nothing enqueued: E outside 1..PEANUT_GOAL_MAX_BATCH, a null or
+ * repeated handle, handles that differ in full_h, full_w, col_rad or in the solver options (fmm_blocked, fmm_local32, fmm_inner,
+ * fmm_max_passes), local windows of different sizes, bad boundaries, a missing target_pred where the mode needs one.
+ * All arrays are HOST arrays of E entries; lmb [E][4] and loc_rc [E][2] as in the single calls; collision_map / visited_vis may be
+ * NULL as arrays or per entry. */
+#define PEANUT_GOAL_MAX_BATCH 16
+/* peanut_goal_select_begin for E handles: traversible maps, initialisation and the first batch of stage-A rounds of all
+ * E episodes on a side stream behind this point of `stream`; no synchronisation.  Taken over by the peanut_goal_select_batch that
+ * names the same handles in the same order with the same inputs; any other call on one of its handles lets the begun work run
+ * out first and then does what it would have done alone. */
+int peanut_goal_select_begin_batch(int E, peanut_goal_t* const* g, const float* const* full_obstacle,
+                                   const uint8_t* const* collision_map, const uint8_t* const* visited_vis,
+                                   const int* lmb, const int* loc_rc, void* stream);
+/* peanut_goal_select for E handles.  target_pred: E device pointers (NULL as an array or per entry only with
+ * dist_weight_temperature == 0); goal_rc_out host [E][2]; stats_out host [E][4] (optional; [e][3] = the rounds the BATCH enqueued,
+ * the same for every e); dist_out / value_out: optional host arrays of E optional device pointers.  peanut_goal_passes /
+ * _converged answer per handle from the episode's own counters.  Synchronises, as the single call does (the solver polls its
+ * counters; one read-back of all E results at the end). */
+int peanut_goal_select_batch(int E, peanut_goal_t* const* g, const float* const* full_obstacle,
+                             const uint8_t* const* collision_map, const uint8_t* const* visited_vis,
+                             const int* lmb, const int* loc_rc, const float* const* target_pred,
+                             double dist_weight_temperature, int map_resolution, int* goal_rc_out, double* stats_out,
+                             double* const* dist_out, double* const* value_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: collation of the predicted maps for logging.  One process per GPU, maps /

@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 16    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 17    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -140,6 +140,11 @@ SIGNATURES = {
     "peanut_fmm_distance": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "peanut_goal_select": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int * 4), C.c_int, C.c_int, _P, C.c_double, C.c_int,
                                      C.POINTER(C.c_int * 2), C.POINTER(C.c_double * 4), _P, _P, _P]),
+    "peanut_goal_select_begin_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "peanut_goal_select_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.POINTER(_P), C.c_double, C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_double), C.POINTER(_P), C.POINTER(_P), _P]),
     "peanut_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_destroy": (None, [_P]),

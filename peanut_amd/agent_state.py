@@ -275,6 +275,11 @@ class Agent_State:
             # update_global_goal follows at once (update_state, :240-245): its geodesic field needs the map as it is NOW, not
             # the prediction -- begun here, the solver runs it on its own stream beside the forward below (include/peanut_hip.h)
             self._goal_solver().select_begin(self.full_map[0], self.collision_map, self.visited_vis, self.lmb, (self.loc_r, self.loc_c))
+        return self._prediction_crop()
+
+    def _prediction_crop(self):
+        """The [1,C,W,W] window of the full map the prediction model reads."""
+        args = self.args
         if self.full_w == args.prediction_window and self.full_h == args.prediction_window:
             return self.full_map[None].contiguous()
         x1 = self.full_w // 2 - args.prediction_window // 2
@@ -312,11 +317,19 @@ class Agent_State:
         """Geodesic-distance-weighted argmax of the target prediction (csrc/goal.hip).  Needs ``target_pred`` (from
         ``update_prediction``) unless ``dist_weight_temperature == 0``."""
         args = self.args
-        res = self._goal_solver().select(self.full_map[0], self.collision_map, self.visited_vis, self.lmb, (self.loc_r, self.loc_c),
-                                self.target_pred, float(getattr(args, "dist_weight_temperature", 500)), int(args.map_resolution))
+        res = self._goal_solver().select(*self._goal_inputs(), self.target_pred, float(getattr(args, "dist_weight_temperature", 500)),
+                                         int(args.map_resolution))
+        self._goal_result(res)
+
+    def _goal_inputs(self):
+        """What the goal solver reads of this episode: (full_obstacle, collision_map, visited_vis, lmb, loc_rc)."""
+        return self.full_map[0], self.collision_map, self.visited_vis, self.lmb, (self.loc_r, self.loc_c)
+
+    def _goal_result(self, res):
+        """The host bookkeeping of ``update_global_goal`` (:410-415) from one ``select`` / ``select_batch`` result."""
         self.value_max = res["value_max"]
         self.goal_rounds = res["rounds"]
-        self.goal_passes, self.goal_converged = self._goal.passes, self._goal.converged
+        self.goal_passes, self.goal_converged = res["passes"], res["converged"]
         new_global_goal = [res["goal"]]
         if new_global_goal != self.last_global_goal:      # avoid repeating the last goal
             self.last_global_goal = self.global_goals
@@ -372,7 +385,10 @@ class Agent_State_Group:
     decisions of ``update_local_map`` per episode, one ``peanut_map_mark_agent_batch``, then per episode exactly what
     ``Agent_State.update_state`` does afterwards.  Every episode ends a step with the bits it would have stepping alone.
     ``batch_predictions=True`` runs the episodes that predict on the same step through one ``get_prediction_batch`` call; a
-    batched forward differs from batch 1 in the last fp32 bits, hence opt-in.
+    batched forward differs from batch 1 in the last fp32 bits, hence opt-in.  ``batch_goals`` (default on): when at least two
+    episodes predict on a step with ``select_goal`` on, their long-term goals are selected in ONE batched solve
+    (``goal.select_batch``: the launches and synchronisations of one solve instead of E in a row), begun for all of them before
+    their prediction forwards; every episode's field, weights and goal are the bits of its own ``update_global_goal``.
 
     The states share one ``Semantic_Mapping`` handle, reserved for ``max_batch`` episodes (default: all of them).  The batch
     is ``self.active``, in order; ``drop`` takes an episode out (it ended), ``reset_active`` puts all back."""
@@ -381,7 +397,7 @@ class Agent_State_Group:
                   "du_scale", "cat_pred_threshold", "exp_pred_threshold", "map_pred_threshold", "num_sem_categories",
                   "camera_height", "col_rad")
 
-    def __init__(self, states, max_batch=None, batch_predictions=False):
+    def __init__(self, states, max_batch=None, batch_predictions=False, batch_goals=True):
         states = list(states)
         if not states:
             raise ValueError("Agent_State_Group needs at least one state")
@@ -403,6 +419,8 @@ class Agent_State_Group:
         self.active = list(states)
         self.device = first.device
         self.batch_predictions = bool(batch_predictions)
+        self.batch_goals = bool(batch_goals)
+        self.goal_batches = 0              # select_batch calls so far (diagnostics)
         self.sem_map_module = first.sem_map_module
         self.sem_map_module.reserve(max_batch)
         for s in states:
@@ -449,6 +467,18 @@ class Agent_State_Group:
             rc = _lib.load().peanut_map_mark_agent_batch(E, maps, int(lm0.shape[0]), m, squares, self.active[0]._selem_mask.data_ptr(),
                                                          rad, n_centres, centres, _lib.current_stream_ptr(self.device))
         _lib.check(rc, "peanut_map_mark_agent_batch")
+
+    def _goal_begin_batch(self, states):
+        """One ``select_begin_batch`` for these episodes (their full maps are final here)."""
+        from .goal import select_begin_batch
+        select_begin_batch([s._goal_solver() for s in states], [s._goal_inputs() for s in states])
+
+    def _goal_select_batch(self, states):
+        """One ``select_batch`` for these episodes -> their E result dicts."""
+        from .goal import select_batch
+        args = states[0].args
+        return select_batch([s._goal_solver() for s in states], [s._goal_inputs() for s in states], [s.target_pred for s in states],
+                            float(getattr(args, "dist_weight_temperature", 500)), int(args.map_resolution))
 
     def _predict_batch(self, crops):
         """One prediction forward over the windows of the episodes that predict on this step -> [n,K,W,W]."""
@@ -513,6 +543,9 @@ class Agent_State_Group:
             s.goal_cat = i['goal_cat_id']
         self.update_local_maps(obs, [i['sensor_pose'] for i in infos])
         predicted = [False] * E
+        batch = self._goal_batch([s for s in act if s._prediction_due()]) if self.batch_goals else []
+        if batch:
+            return self._update_state_goal_batch(act, batch)
         if not self.batch_predictions:
             for e, s in enumerate(act):
                 s._step_full_map()
@@ -538,3 +571,56 @@ class Agent_State_Group:
         for s in act:
             s.inc_step()
         return predicted
+
+    def _update_state_goal_batch(self, act, batch):
+        """The rest of ``update_state`` on a step on which the episodes of ``batch`` (>= 2) select their goals in one solve: local
+        periods, write-back of the batch's local maps, ONE begin, the prediction forwards (the batch's beside their E fields), the
+        single way for the other due episodes, ONE ``select_batch``, the host bookkeeping per episode."""
+        predicted = [False] * len(act)
+        for s in act:
+            s._step_full_map()
+        due = [e for e, s in enumerate(act) if s._prediction_due()]
+        in_batch = {id(s) for s in batch}
+        for s in batch:
+            s.full_map[:, s.lmb[0]:s.lmb[1], s.lmb[2]:s.lmb[3]] = s.local_map
+        if getattr(batch[0].args, "goal_overlap", True):
+            self._goal_begin_batch(batch)
+        if not self.batch_predictions:
+            for e in due:
+                s = act[e]
+                if id(s) in in_batch:
+                    s._prediction_output(s.prediction_model.get_prediction_batch(s._prediction_crop())[0])
+                else:
+                    select = getattr(s.args, "select_goal", True)
+                    s.update_prediction(goal_follows=select)
+                    if select:
+                        s.update_global_goal()
+                predicted[e] = True
+        else:
+            crops = [act[e]._prediction_crop() if id(act[e]) in in_batch else
+                     act[e]._prediction_input(getattr(act[e].args, "select_goal", True)) for e in due]
+            preds = self._predict_batch(crops)
+            for k, e in enumerate(due):
+                act[e]._prediction_output(preds[k])
+                if id(act[e]) not in in_batch and getattr(act[e].args, "select_goal", True):
+                    act[e].update_global_goal()
+                predicted[e] = True
+        self.goal_batches += 1
+        for s, res in zip(batch, self._goal_select_batch(batch)):
+            s._goal_result(res)
+        for s in act:
+            s.inc_step()
+        return predicted
+
+    @staticmethod
+    def _goal_batch(due_states):
+        """The episodes of this step whose goals go through one batched solve: those with ``select_goal`` on that agree with the
+        first such episode in what the batch call takes once (``dist_weight_temperature``, ``map_resolution``, ``goal_overlap``) and
+        in the map size; fewer than two -> none (they go the single way)."""
+        from .goal import MAX_BATCH
+        def key(s):
+            return (float(getattr(s.args, "dist_weight_temperature", 500)), int(s.args.map_resolution),
+                    bool(getattr(s.args, "goal_overlap", True)), s.full_w, s.full_h, s.local_w, s.local_h, int(s.args.col_rad))
+        sel = [s for s in due_states if getattr(s.args, "select_goal", True)]
+        sel = [s for s in sel if key(s) == key(sel[0])][:MAX_BATCH]
+        return sel if len(sel) >= 2 else []

@@ -46,6 +46,12 @@
 // batch of relaxation rounds on a stream of the handle at once; the forward the caller enqueues next (Agent_State.update_state:
 // update_prediction then update_global_goal) runs beside them, peanut_goal_select continues the solve on that stream, and the
 // caller's stream joins before the weights are formed.
+//
+// Several episodes (Agent_State_Group: E episodes per GPU in lock-step select their goals on the same steps): a round wakes a ring of
+// tiles and costs the latency of one, so E solves in a row leave most CUs idle E times over and synchronise E times per stage.
+// peanut_goal_select_batch runs up to PEANUT_GOAL_MAX_BATCH episodes in the launches and synchronisations of ONE solve: a round is
+// one launch over (tiles, E), a check one read-back of the [E][rounds] counters.  Every episode keeps its own handle and sees the
+// rounds of its own solve with rounds that wake none of its tiles in between -- its results are the bits of peanut_goal_select.
 #include <math.h>
 #include <stdlib.h>
 
@@ -66,14 +72,33 @@ constexpr int MAX_ORDER_PASSES = 24;    // default of option fmm_max_passes: a c
 
 enum : unsigned char { ST_MASKED = 0, ST_FREE = 1, ST_SEED = 2 };
 
+// Every kernel below exists twice: for one episode, and for up to GB episodes in one launch (peanut_goal_select_batch: the
+// episode is blockIdx.y -- blockIdx.z for the two-dimensional traversible grid -- and the per-episode pointers and scalars travel
+// by value in a struct of GB slots).  Both are thin wrappers around ONE __device__ body, so an expression two kernels must agree on
+// bit for bit lives in one function.
+constexpr int GB = PEANUT_GOAL_MAX_BATCH;
+struct TravBatchArgs {
+  const float* obst[GB];
+  const unsigned char *col[GB], *vis[GB];
+  unsigned char* trav[GB];
+};
+struct FieldBatchArgs {
+  double* dist[GB];
+  double* ord[GB];
+  unsigned char* state[GB];
+  unsigned char* active[GB];      // four flag arrays of tiles_x * tiles_y bytes each (field_preamble)
+  int seed_r[GB], seed_c[GB];
+  unsigned int done;              // bit e: episode e takes no part in this launch (its passes ended, or its stage has settled)
+};
+
 // ---- traversible map: ~dilate(rint(obstacle), disk(rad)), collision -> 0, visited -> 1  (agent_state.py:382-386) ----
 // A workgroup covers 32 x 8 cells.  The obstacle bits of its rows (8 + 2 rad of them, 32 + 2 rad columns wide: one 64-bit word per
 // row while rad <= 16) are formed once with a ballot per row; a cell is blocked when any row of its disk has an obstacle bit under
 // that row's chord -- 2 rad + 1 AND-tests instead of (2 rad + 1)^2 loads (85 -> ~12 us on the 960 x 960 map).
 constexpr int TRAV_MAX_RAD = 16;
-__global__ __launch_bounds__(256) void goal_trav_kernel(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
-                                                        const unsigned char* __restrict__ visited, int H, int W, int rad,
-                                                        unsigned char* __restrict__ trav) {
+__device__ __forceinline__ void goal_trav_body(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
+                                               const unsigned char* __restrict__ visited, int H, int W, int rad,
+                                               unsigned char* __restrict__ trav) {
   __shared__ unsigned long long rowbits[8 + 2 * TRAV_MAX_RAD];
   __shared__ int chord[2 * TRAV_MAX_RAD + 1];      // half-width of the disk at row offset dy
   const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 8;
@@ -108,10 +133,19 @@ __global__ __launch_bounds__(256) void goal_trav_kernel(const float* __restrict_
   if (visited && visited[i] == 1) t = 1;
   trav[i] = t;
 }
+__global__ __launch_bounds__(256) void goal_trav_kernel(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
+                                                        const unsigned char* __restrict__ visited, int H, int W, int rad,
+                                                        unsigned char* __restrict__ trav) {
+  goal_trav_body(obst, collision, visited, H, W, rad, trav);
+}
+__global__ __launch_bounds__(256) void goal_trav_batch_kernel(TravBatchArgs a, int H, int W, int rad) {
+  const int e = blockIdx.z;
+  goal_trav_body(a.obst[e], a.col[e], a.vis[e], H, W, rad, a.trav[e]);
+}
 // any radius (the footprint test cell by cell): used beyond TRAV_MAX_RAD
-__global__ __launch_bounds__(256) void goal_trav_wide_kernel(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
-                                                             const unsigned char* __restrict__ visited, int H, int W, int rad,
-                                                             unsigned char* __restrict__ trav) {
+__device__ __forceinline__ void goal_trav_wide_body(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
+                                                    const unsigned char* __restrict__ visited, int H, int W, int rad,
+                                                    unsigned char* __restrict__ trav) {
   const int c = blockIdx.x * 32 + (threadIdx.x & 31), r = blockIdx.y * 8 + (threadIdx.x >> 5);
   if (r >= H || c >= W) return;
   bool blocked = false;
@@ -132,17 +166,48 @@ __global__ __launch_bounds__(256) void goal_trav_wide_kernel(const float* __rest
   trav[i] = t;
 }
 
-// state / distance initialisation: masked where not traversible, seeds (one cell and/or a mask) at distance 0
-__global__ __launch_bounds__(256) void fmm_init_kernel(const unsigned char* __restrict__ trav, const unsigned char* __restrict__ seed_mask,
-                                                       int seed_r, int seed_c, int H, int W, unsigned char* __restrict__ state,
-                                                       double* __restrict__ dist, unsigned char* __restrict__ active, int tiles_x) {
+__global__ __launch_bounds__(256) void goal_trav_wide_kernel(const float* __restrict__ obst, const unsigned char* __restrict__ collision,
+                                                             const unsigned char* __restrict__ visited, int H, int W, int rad,
+                                                             unsigned char* __restrict__ trav) {
+  goal_trav_wide_body(obst, collision, visited, H, W, rad, trav);
+}
+__global__ __launch_bounds__(256) void goal_trav_wide_batch_kernel(TravBatchArgs a, int H, int W, int rad) {
+  const int e = blockIdx.z;
+  goal_trav_wide_body(a.obst[e], a.col[e], a.vis[e], H, W, rad, a.trav[e]);
+}
+
+// state / distance initialisation: masked where not traversible, seeds (one cell and/or a mask) at distance 0.  `active`: the seeds'
+// tiles are flagged there; `active2` (optional): and there -- the batched form flags the seed-tile array and the first round's input
+// in one launch, where the single solve copies one to the other.
+__device__ __forceinline__ void fmm_init_body(const unsigned char* __restrict__ trav, const unsigned char* __restrict__ seed_mask,
+                                              int seed_r, int seed_c, int H, int W, unsigned char* __restrict__ state,
+                                              double* __restrict__ dist, unsigned char* __restrict__ active,
+                                              unsigned char* __restrict__ active2, int tiles_x) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= H * W) return;
   const int r = i / W, c = i - r * W;
   const bool seed = (r == seed_r && c == seed_c) || (seed_mask && seed_mask[i] == 1);
   state[i] = seed ? ST_SEED : (trav[i] ? ST_FREE : ST_MASKED);
   dist[i] = seed ? 0.0 : INFINITY;
-  if (seed) active[(r / TILE) * tiles_x + (c / TILE)] = 1;
+  if (seed) {
+    active[(r / TILE) * tiles_x + (c / TILE)] = 1;
+    if (active2) active2[(r / TILE) * tiles_x + (c / TILE)] = 1;
+  }
+}
+__global__ __launch_bounds__(256) void fmm_init_kernel(const unsigned char* __restrict__ trav, const unsigned char* __restrict__ seed_mask,
+                                                       int seed_r, int seed_c, int H, int W, unsigned char* __restrict__ state,
+                                                       double* __restrict__ dist, unsigned char* __restrict__ active, int tiles_x) {
+  fmm_init_body(trav, seed_mask, seed_r, seed_c, H, W, state, dist, active, nullptr, tiles_x);
+}
+// all four flag arrays of every episode to zero: the batched solve's memset (one launch instead of E)
+__global__ __launch_bounds__(256) void fmm_flags_clear_batch_kernel(FieldBatchArgs a, int nflags) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < nflags) a.active[blockIdx.y][i] = 0;
+}
+__global__ __launch_bounds__(256) void fmm_init_batch_kernel(FieldBatchArgs a, TravBatchArgs t, int H, int W, int tiles_x, int nt) {
+  const int e = blockIdx.y;
+  unsigned char* act = a.active[e];
+  fmm_init_body(t.trav[e], nullptr, a.seed_r[e], a.seed_c[e], H, W, a.state[e], a.dist[e], act + 3 * (size_t)nt, act, tiles_x);
 }
 
 // one axis of distanceMarcher::updatePointOrderTwo.  m1/m2 = the values one and two steps towards smaller indices,
@@ -290,10 +355,10 @@ __device__ __forceinline__ double update_cell_local_fast(double ym1, double ym2,
 // quadratic solved in single precision relative to the smaller upwind value (update_cell_local).  `active_clear`
 // (the flags of the round after next) is wiped here, one byte per tile, which saves a fill launch per round.
 template <bool SECOND, bool LOCAL32>
-__global__ __launch_bounds__(1024) void fmm_round_kernel(double* __restrict__ dist, const double* __restrict__ ord,
-                                                         const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
-                                                         const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
-                                                         unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles) {
+__device__ __forceinline__ void fmm_round_body(double* __restrict__ dist, const double* __restrict__ ord,
+                                               const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
+                                               const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
+                                               unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles) {
   const int tile = blockIdx.x;
   if (threadIdx.x == 0) active_clear[tile] = 0;
   if (!active_in[tile]) return;
@@ -387,6 +452,28 @@ __global__ __launch_bounds__(1024) void fmm_round_kernel(double* __restrict__ di
   }
 }
 
+template <bool SECOND, bool LOCAL32>
+__global__ __launch_bounds__(1024) void fmm_round_kernel(double* __restrict__ dist, const double* __restrict__ ord,
+                                                         const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
+                                                         const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
+                                                         unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles) {
+  fmm_round_body<SECOND, LOCAL32>(dist, ord, state, H, W, tiles_x, tiles_y, active_in, active_out, active_clear, changed_tiles);
+}
+// The round of up to GB episodes: grid (tiles, E).  `cur` = the rotation of the three flag arrays (the same for every episode: they
+// take their rounds together); `counters` [E][MAX_ROUNDS_PER_CHECK], this round's column k.  An episode whose `done` bit is set
+// returns at once, as a sleeping tile does.
+template <bool SECOND, bool LOCAL32>
+__global__ __launch_bounds__(1024) void fmm_round_batch_kernel(FieldBatchArgs a, int H, int W, int tiles_x, int tiles_y, int cur,
+                                                               unsigned int* __restrict__ counters, int k) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  const int nt = tiles_x * tiles_y;
+  unsigned char* act = a.active[e];
+  fmm_round_body<SECOND, LOCAL32>(a.dist[e], a.ord[e], a.state[e], H, W, tiles_x, tiles_y, act + (size_t)cur * nt,
+                                  act + (size_t)((cur + 1) % 3) * nt, act + (size_t)((cur + 2) % 3) * nt,
+                                  counters + e * MAX_ROUNDS_PER_CHECK + k);
+}
+
 // The same round, blocked (round 5).  In the kernel above the front moves one cell per sweep and every sweep costs two
 // workgroup barriers over 16 waves plus the change-tracking reads: ~1.1 us per sweep, 70-90 us for a front to cross a tile,
 // and a round costs exactly that (only a ring of tiles is awake, so rounds are latency, not throughput).  Here a wave owns
@@ -399,11 +486,11 @@ __global__ __launch_bounds__(1024) void fmm_round_kernel(double* __restrict__ di
 // fixed dependency graph make the result independent of the schedule up to the update's own noise floor.
 constexpr int BLK = 8, PT = BLK + 2 * HALO, MAX_OUTER = 64;      // private tile 12 x 12
 template <bool SECOND, bool LOCAL32>
-__global__ __launch_bounds__(1024) void fmm_round_blocked_kernel(double* __restrict__ dist, const double* __restrict__ ord,
-                                                                 const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
-                                                                 const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
-                                                                 unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles,
-                                                                 int max_inner) {
+__device__ __forceinline__ void fmm_round_blocked_body(double* __restrict__ dist, const double* __restrict__ ord,
+                                                       const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
+                                                       const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
+                                                       unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles,
+                                                       int max_inner) {
   const int tile = blockIdx.x;
   if (threadIdx.x == 0) active_clear[tile] = 0;
   if (!active_in[tile]) return;
@@ -524,10 +611,49 @@ __global__ __launch_bounds__(1024) void fmm_round_blocked_kernel(double* __restr
   }
 }
 
+template <bool SECOND, bool LOCAL32>
+__global__ __launch_bounds__(1024) void fmm_round_blocked_kernel(double* __restrict__ dist, const double* __restrict__ ord,
+                                                                 const unsigned char* __restrict__ state, int H, int W, int tiles_x, int tiles_y,
+                                                                 const unsigned char* __restrict__ active_in, unsigned char* __restrict__ active_out,
+                                                                 unsigned char* __restrict__ active_clear, unsigned int* __restrict__ changed_tiles,
+                                                                 int max_inner) {
+  fmm_round_blocked_body<SECOND, LOCAL32>(dist, ord, state, H, W, tiles_x, tiles_y, active_in, active_out, active_clear, changed_tiles,
+                                          max_inner);
+}
+template <bool SECOND, bool LOCAL32>
+__global__ __launch_bounds__(1024) void fmm_round_blocked_batch_kernel(FieldBatchArgs a, int H, int W, int tiles_x, int tiles_y, int cur,
+                                                                       unsigned int* __restrict__ counters, int k, int max_inner) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  const int nt = tiles_x * tiles_y;
+  unsigned char* act = a.active[e];
+  fmm_round_blocked_body<SECOND, LOCAL32>(a.dist[e], a.ord[e], a.state[e], H, W, tiles_x, tiles_y, act + (size_t)cur * nt,
+                                          act + (size_t)((cur + 1) % 3) * nt, act + (size_t)((cur + 2) % 3) * nt,
+                                          counters + e * MAX_ROUNDS_PER_CHECK + k, max_inner);
+}
+
 // stage B starts from the seeds again: distances back to +inf (seeds 0)
-__global__ __launch_bounds__(256) void fmm_restart_kernel(const unsigned char* __restrict__ state, int n, double* __restrict__ dist) {
+__device__ __forceinline__ void fmm_restart_body(const unsigned char* __restrict__ state, int n, double* __restrict__ dist) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) dist[i] = state[i] == ST_SEED ? 0.0 : INFINITY;
+}
+__global__ __launch_bounds__(256) void fmm_restart_kernel(const unsigned char* __restrict__ state, int n, double* __restrict__ dist) {
+  fmm_restart_body(state, n, dist);
+}
+// What the host issues between two stages of the single solve (order <- dist; pass 0: the restart, the three flag arrays wiped, the
+// seed tiles awake; later passes: every tile awake), for every episode that still takes passes, in one launch.  `cur`: the flag array
+// the next round reads.
+__global__ __launch_bounds__(256) void fmm_pass_batch_kernel(FieldBatchArgs a, int n, int nt, int restart, int cur) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) a.ord[e][i] = a.dist[e][i];
+  if (restart) fmm_restart_body(a.state[e], n, a.dist[e]);
+  if (i < nt) {
+    unsigned char* act = a.active[e];
+    const unsigned char wake = restart ? act[3 * (size_t)nt + i] : (unsigned char)1;
+    for (int j = 0; j < 3; ++j) act[(size_t)j * nt + i] = j == cur ? wake : (unsigned char)0;
+  }
 }
 
 // max over the reached cells (for `ma.filled(dd, np.max(dd) + 1)`); bits of a non-negative double order like an integer
@@ -551,19 +677,22 @@ __global__ __launch_bounds__(256) void fmm_fill_kernel(const double* __restrict_
 // max over ALL cells, +inf included (for `dd[dd == np.max(dd)] = np.inf` after the fill, :392-393): +inf when some cell is masked or
 // unreached -- the rule then turns exactly those (filled with max + 1) into +inf, which they already are -- else the farthest
 // reached distance, whose cells the rule turns into +inf too.  Bits of a non-negative double order like an integer.
-__global__ __launch_bounds__(256) void goal_field_max_kernel(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
+__device__ __forceinline__ void goal_field_max_body(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
   double m = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = fmax(m, dist[i]);
   for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
   if ((threadIdx.x & 63) == 0) atomicMax(max_bits, (unsigned long long)__double_as_longlong(m));
 }
+__global__ __launch_bounds__(256) void goal_field_max_kernel(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
+  goal_field_max_body(dist, n, max_bits);
+}
 
 // ---- weights over the local window: exp(-dd / temperature) (:395-396), their sum (:398) ----
 // One partial sum per workgroup (fixed order inside it); goal_sum_kernel adds the partials in index order, so the sum -- and the
 // "sum < 10: keep the last weights" decision -- is the same bits on every run.
-__global__ __launch_bounds__(256) void goal_weight_kernel(const double* __restrict__ dist, int W, int gx1, int gy1, int lw, int lh,
-                                                          double temperature, int frontier, const unsigned long long* __restrict__ field_max,
-                                                          double* __restrict__ wt, double* __restrict__ part_out) {
+__device__ __forceinline__ void goal_weight_body(const double* __restrict__ dist, int W, int gx1, int gy1, int lw, int lh,
+                                                 double temperature, int frontier, const unsigned long long* __restrict__ field_max,
+                                                 double* __restrict__ wt, double* __restrict__ part_out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const double dmax = __longlong_as_double((long long)*field_max);
   double w = 0.0;
@@ -585,8 +714,13 @@ __global__ __launch_bounds__(256) void goal_weight_kernel(const double* __restri
   __syncthreads();
   if (threadIdx.x == 0) part_out[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
+__global__ __launch_bounds__(256) void goal_weight_kernel(const double* __restrict__ dist, int W, int gx1, int gy1, int lw, int lh,
+                                                          double temperature, int frontier, const unsigned long long* __restrict__ field_max,
+                                                          double* __restrict__ wt, double* __restrict__ part_out) {
+  goal_weight_body(dist, W, gx1, gy1, lw, lh, temperature, frontier, field_max, wt, part_out);
+}
 // the partials of goal_weight_kernel in a fixed order: lane t adds t, t + 256, ... in turn, then a fixed tree
-__global__ __launch_bounds__(256) void goal_sum_kernel(const double* __restrict__ part, int nparts, double* __restrict__ sum) {
+__device__ __forceinline__ void goal_sum_body(const double* __restrict__ part, int nparts, double* __restrict__ sum) {
   double w = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 256) w += part[i];
   for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o);
@@ -594,6 +728,9 @@ __global__ __launch_bounds__(256) void goal_sum_kernel(const double* __restrict_
   if ((threadIdx.x & 63) == 0) p[threadIdx.x >> 6] = w;
   __syncthreads();
   if (threadIdx.x == 0) *sum = (p[0] + p[1]) + (p[2] + p[3]);
+}
+__global__ __launch_bounds__(256) void goal_sum_kernel(const double* __restrict__ part, int nparts, double* __restrict__ sum) {
+  goal_sum_body(part, nparts, sum);
 }
 
 // value = target_pred * dd_wt (or one of them alone) and its first-occurrence argmax (:401-413); two stages.
@@ -606,9 +743,9 @@ __device__ __forceinline__ bool beats(ArgMax b, ArgMax a) {
   return (bn || b.v == a.v) ? b.i < a.i : b.v > a.v;
 }
 __device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) { return beats(b, a) ? b : a; }
-__global__ __launch_bounds__(256) void goal_argmax_kernel(const float* __restrict__ target_pred, const double* __restrict__ wt_new,
-                                                          const double* __restrict__ wt_last, const double* __restrict__ sum, int have_last,
-                                                          int mode, int n, double* __restrict__ value_out, ArgMax* __restrict__ partial) {
+__device__ __forceinline__ void goal_argmax_body(const float* __restrict__ target_pred, const double* __restrict__ wt_new,
+                                                 const double* __restrict__ wt_last, const double* __restrict__ sum, int have_last,
+                                                 int mode, int n, double* __restrict__ value_out, ArgMax* __restrict__ partial) {
   // mode 0: target_pred * wt, 1: target_pred alone (temperature -1), 2: wt alone (temperature 0)
   const bool keep_last = mode != 2 && have_last && *sum < 10.0;      // (:398) "stuck inside obstacle, use last dd_wt"
   const double* wt = keep_last ? wt_last : wt_new;
@@ -628,10 +765,15 @@ __global__ __launch_bounds__(256) void goal_argmax_kernel(const float* __restric
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = better(better(part[0], part[1]), better(part[2], part[3]));
 }
-__global__ __launch_bounds__(64) void goal_argmax_final_kernel(const ArgMax* __restrict__ partial, int nparts, const double* __restrict__ sum,
-                                                               int have_last, int mode, const double* __restrict__ wt_new,
-                                                               double* __restrict__ wt_last, int n, int* __restrict__ out_idx,
-                                                               double* __restrict__ out_val) {
+__global__ __launch_bounds__(256) void goal_argmax_kernel(const float* __restrict__ target_pred, const double* __restrict__ wt_new,
+                                                          const double* __restrict__ wt_last, const double* __restrict__ sum, int have_last,
+                                                          int mode, int n, double* __restrict__ value_out, ArgMax* __restrict__ partial) {
+  goal_argmax_body(target_pred, wt_new, wt_last, sum, have_last, mode, n, value_out, partial);
+}
+__device__ __forceinline__ void goal_argmax_final_body(const ArgMax* __restrict__ partial, int nparts, const double* __restrict__ sum,
+                                                       int have_last, int mode, const double* __restrict__ wt_new,
+                                                       double* __restrict__ wt_last, int n, int* __restrict__ out_idx,
+                                                       double* __restrict__ out_val) {
   ArgMax best{-INFINITY, 0x7fffffff};
   for (int i = threadIdx.x; i < nparts; i += 64) best = better(best, partial[i]);
   for (int o = 32; o > 0; o >>= 1) {
@@ -645,11 +787,86 @@ __global__ __launch_bounds__(64) void goal_argmax_final_kernel(const ArgMax* __r
     out_val[1] = *sum;
   }
 }
+__global__ __launch_bounds__(64) void goal_argmax_final_kernel(const ArgMax* __restrict__ partial, int nparts, const double* __restrict__ sum,
+                                                               int have_last, int mode, const double* __restrict__ wt_new,
+                                                               double* __restrict__ wt_last, int n, int* __restrict__ out_idx,
+                                                               double* __restrict__ out_val) {
+  goal_argmax_final_body(partial, nparts, sum, have_last, mode, wt_new, wt_last, n, out_idx, out_val);
+}
+
+// ---- the same five for up to GB episodes: grid (what the single kernel takes, E) ----
+struct GoalResult {             // per episode, read back in one copy
+  unsigned long long field_max;
+  double val[2];                // value max, sum of the fresh weights
+  int idx[2];                   // argmax, 1 if the last weights were kept
+};
+struct SelectBatchArgs {
+  const double* dist[GB];
+  const float* target_pred[GB];
+  double *wt_new[GB], *wt_last[GB], *wt_part[GB], *sum[GB], *value[GB];
+  ArgMax* partial[GB];
+  int gx1[GB], gy1[GB], have_last[GB];
+  GoalResult* res;              // [E]
+};
+__global__ __launch_bounds__(256) void goal_field_max_batch_kernel(SelectBatchArgs a, int n) {
+  const int e = blockIdx.y;
+  goal_field_max_body(a.dist[e], n, &a.res[e].field_max);
+}
+__global__ __launch_bounds__(256) void goal_weight_batch_kernel(SelectBatchArgs a, int W, int lw, int lh, double temperature, int frontier) {
+  const int e = blockIdx.y;
+  goal_weight_body(a.dist[e], W, a.gx1[e], a.gy1[e], lw, lh, temperature, frontier, &a.res[e].field_max, a.wt_new[e], a.wt_part[e]);
+}
+__global__ __launch_bounds__(256) void goal_sum_batch_kernel(SelectBatchArgs a, int nparts) {
+  const int e = blockIdx.y;
+  goal_sum_body(a.wt_part[e], nparts, a.sum[e]);
+}
+__global__ __launch_bounds__(256) void goal_argmax_batch_kernel(SelectBatchArgs a, int mode, int n) {
+  const int e = blockIdx.y;
+  goal_argmax_body(a.target_pred[e], a.wt_new[e], a.wt_last[e], a.sum[e], a.have_last[e], mode, n, a.value[e], a.partial[e]);
+}
+__global__ __launch_bounds__(64) void goal_argmax_final_batch_kernel(SelectBatchArgs a, int nparts, int mode, int n) {
+  const int e = blockIdx.y;
+  goal_argmax_final_body(a.partial[e], nparts, a.sum[e], a.have_last[e], mode, a.wt_new[e], a.wt_last[e], n, a.res[e].idx, a.res[e].val);
+}
+// self.dd_wt = dd_wt (:410): the fresh weights become the last ones unless the old ones were kept -- the copy the single call
+// issues after its read-back, decided on the device from the flag goal_argmax_final wrote
+__global__ __launch_bounds__(256) void goal_keep_batch_kernel(SelectBatchArgs a, int n) {
+  const int e = blockIdx.y;
+  if (a.res[e].idx[1]) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) a.wt_last[e][i] = a.wt_new[e][i];
+}
 
 }  // namespace
 }  // namespace peanut
 
 using namespace peanut;
+
+// What a batched select needs beyond the episodes' own handles; owned by the FIRST handle of the batch, made on first use.
+struct GoalBatch {
+  hipStream_t side = nullptr;              // as peanut_goal::side, for the fields of a begun batch
+  hipEvent_t ev_inputs = nullptr, ev_field = nullptr;
+  DevBuf counters, results;                // [GB][MAX_ROUNDS_PER_CHECK] "tiles changed" per episode and round; [GB] GoalResult
+  unsigned int* host_counters = nullptr;   // pinned mirrors
+  GoalResult* host_results = nullptr;
+  // peanut_goal_select_begin_batch: what is on `side`, for whom and from which inputs
+  struct Begun {
+    bool on = false;
+    int E = 0, batch = 0, cur = 0;
+    peanut_goal* g[GB] = {nullptr};
+    const float* obst[GB] = {nullptr};
+    const unsigned char *col[GB] = {nullptr}, *vis[GB] = {nullptr};
+    int lmb[GB][4] = {{0}}, loc[GB][2] = {{0}};
+  } begun;
+  ~GoalBatch() {
+    if (ev_inputs) (void)hipEventDestroy(ev_inputs);
+    if (ev_field) (void)hipEventDestroy(ev_field);
+    if (side) (void)hipStreamDestroy(side);
+    if (host_counters) (void)hipHostFree(host_counters);
+    if (host_results) (void)hipHostFree(host_results);
+  }
+};
+namespace { void drain_batch_of(peanut_goal* g); }
 
 struct peanut_goal {
   peanut::Options opts = peanut::default_options();   // tuning options of this handle (options.h): snapshot at creation
@@ -672,7 +889,10 @@ struct peanut_goal {
     const unsigned char *col = nullptr, *vis = nullptr;
     int lmb[4] = {0, 0, 0, 0}, loc_r = 0, loc_c = 0, batch = 0, cur = 0;
   } begun;
+  std::shared_ptr<GoalBatch> batch;      // this handle leads batches (it is their first): their shared scratch
+  std::shared_ptr<GoalBatch> begun_in;   // a begun batch this handle is part of: its rounds own the handle's scratch
   ~peanut_goal() {
+    drain_batch_of(this);
     if (ev_inputs) (void)hipEventDestroy(ev_inputs);
     if (ev_field) (void)hipEventDestroy(ev_field);
     if (side) (void)hipStreamDestroy(side);
@@ -681,6 +901,17 @@ struct peanut_goal {
 };
 
 namespace {
+
+// A batch begun with this handle in it and not taken over: its rounds run out, and every handle of it is free again.
+void drain_batch_of(peanut_goal* g) {
+  if (!g->begun_in) return;
+  std::shared_ptr<GoalBatch> B = g->begun_in;
+  (void)hipStreamSynchronize(B->side);
+  for (int e = 0; e < B->begun.E; ++e)
+    if (B->begun.g[e]) { B->begun.g[e]->begun_in.reset(); B->begun.g[e] = nullptr; }
+  B->begun.on = false;
+  B->begun.E = 0;
+}
 
 // `batch` relaxation rounds of a stage and the read-back of their "tiles changed" counters, enqueued (no synchronisation)
 template <bool SECOND>
@@ -823,6 +1054,7 @@ void peanut_goal_destroy(peanut_goal_t* g) { delete g; }
 int peanut_goal_reset(peanut_goal_t* g) {
   if (!g) return fail(PEANUT_EINVAL, "peanut_goal_reset: null handle");
   g->have_last = false;
+  drain_batch_of(g);
   if (g->begun.on) { (void)hipStreamSynchronize(g->side); g->begun.on = false; }
   return 0;
 }
@@ -854,6 +1086,7 @@ int peanut_goal_select_begin(peanut_goal_t* g, const float* full_obstacle, const
   if (lmb[0] < 0 || lmb[2] < 0 || lmb[1] > g->H || lmb[3] > g->W || lmb[1] - lmb[0] < 1 || lmb[3] - lmb[2] < 1)
     return fail(PEANUT_EINVAL, "peanut_goal_select_begin: bad local map boundaries");
   if (int rc = ensure_side(g)) return rc;
+  drain_batch_of(g);
   if (g->begun.on) PEANUT_HIP_CHECK(hipStreamSynchronize(g->side));      // a begin nobody finished: its rounds still own the scratch
   PEANUT_HIP_CHECK(hipEventRecord(g->ev_inputs, (hipStream_t)stream));
   PEANUT_HIP_CHECK(hipStreamWaitEvent(g->side, g->ev_inputs, 0));
@@ -880,6 +1113,312 @@ int peanut_goal_select_begin(peanut_goal_t* g, const float* full_obstacle, const
   return 0;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The solve of up to GB episodes in the launches and synchronisations of one (peanut_goal_select_batch).  Per episode the sequence
+// of EFFECTIVE rounds is the one its own solve_field runs: a stage goes on until every episode's last counter of a check is zero --
+// an episode that has settled takes no part in the stage's further rounds -- the next ordering pass starts for all episodes that
+// still need one, and an episode whose pass changed nothing (pass > 0) is done.  Stage A is a monotone relaxation and stage B a
+// fixed-point sweep on an acyclic graph: the field does not depend on when a round runs, so every episode ends with the bits of its
+// own solve (tests/test_goal_batch_gpu.py holds that with torch.equal).
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int ensure_batch(peanut_goal* lead) {
+  if (lead->batch) return 0;
+  auto B = std::make_shared<GoalBatch>();
+  int prio_least = 0, prio_greatest = 0;      // (as ensure_side)
+  PEANUT_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  PEANUT_HIP_CHECK(hipStreamCreateWithPriority(&B->side, hipStreamNonBlocking, prio_greatest));
+  PEANUT_HIP_CHECK(hipEventCreateWithFlags(&B->ev_inputs, hipEventDisableTiming));
+  PEANUT_HIP_CHECK(hipEventCreateWithFlags(&B->ev_field, hipEventDisableTiming));
+  if (int rc = B->counters.ensure((size_t)GB * MAX_ROUNDS_PER_CHECK * sizeof(unsigned int))) return rc;
+  if (int rc = B->results.ensure((size_t)GB * sizeof(GoalResult))) return rc;
+  PEANUT_HIP_CHECK(hipHostMalloc((void**)&B->host_counters, (size_t)GB * MAX_ROUNDS_PER_CHECK * sizeof(unsigned int), hipHostMallocDefault));
+  PEANUT_HIP_CHECK(hipHostMalloc((void**)&B->host_results, (size_t)GB * sizeof(GoalResult), hipHostMallocDefault));
+  lead->batch = B;
+  return 0;
+}
+
+// the refusals both batched entry points share; nothing is enqueued or waited for before they have passed
+int check_batch(const char* who, int E, peanut_goal_t* const* g, const float* const* full_obstacle, const int* lmb, const int* loc_rc) {
+  const std::string w(who);
+  if (E < 1 || E > GB) return fail(PEANUT_EINVAL, w + ": E must be 1..PEANUT_GOAL_MAX_BATCH");
+  if (!g || !full_obstacle || !lmb || !loc_rc) return fail(PEANUT_EINVAL, w + ": null argument");
+  static const OptionId same[] = {OPT_FMM_BLOCKED, OPT_FMM_LOCAL32, OPT_FMM_INNER, OPT_FMM_MAX_PASSES};
+  for (int e = 0; e < E; ++e) {
+    if (!g[e] || !full_obstacle[e]) return fail(PEANUT_EINVAL, w + ": null handle or obstacle map");
+    for (int f = 0; f < e; ++f)
+      if (g[f] == g[e]) return fail(PEANUT_EINVAL, w + ": the same handle appears twice");
+    if (g[e]->H != g[0]->H || g[e]->W != g[0]->W || g[e]->rad != g[0]->rad)
+      return fail(PEANUT_EINVAL, w + ": the handles differ in map size or collision radius");
+    for (OptionId id : same)
+      if (g[e]->opts.v[id] != g[0]->opts.v[id]) return fail(PEANUT_EINVAL, w + ": the handles differ in their solver options");
+    const int* b = lmb + 4 * e;
+    if (b[0] < 0 || b[2] < 0 || b[1] > g[e]->H || b[3] > g[e]->W || b[1] - b[0] < 1 || b[3] - b[2] < 1)
+      return fail(PEANUT_EINVAL, w + ": bad local map boundaries");
+    if (b[1] - b[0] != lmb[1] - lmb[0] || b[3] - b[2] != lmb[3] - lmb[2])
+      return fail(PEANUT_EINVAL, w + ": the local windows differ in size");
+  }
+  return 0;
+}
+
+// every begun piece of work (single or batch) on one of these handles runs out
+void drain_all(int E, peanut_goal_t* const* g) {
+  for (int e = 0; e < E; ++e) {
+    drain_batch_of(g[e]);
+    if (g[e]->begun.on) { (void)hipStreamSynchronize(g[e]->side); g[e]->begun.on = false; }
+  }
+}
+
+void fill_field_args(int E, peanut_goal_t* const* g, const int* lmb, const int* loc_rc, FieldBatchArgs* fa, TravBatchArgs* ta,
+                     const float* const* obst, const uint8_t* const* col, const uint8_t* const* vis) {
+  *fa = FieldBatchArgs{};
+  *ta = TravBatchArgs{};
+  for (int e = 0; e < E; ++e) {
+    fa->dist[e] = (double*)g[e]->dist.p; fa->ord[e] = (double*)g[e]->order.p;
+    fa->state[e] = (unsigned char*)g[e]->state.p; fa->active[e] = (unsigned char*)g[e]->active.p;
+    seed_cell(g[e], lmb + 4 * e, loc_rc[2 * e], loc_rc[2 * e + 1], &fa->seed_r[e], &fa->seed_c[e]);
+    ta->obst[e] = obst[e]; ta->col[e] = col ? col[e] : nullptr; ta->vis[e] = vis ? vis[e] : nullptr;
+    ta->trav[e] = (unsigned char*)g[e]->trav.p;
+  }
+}
+
+// traversible maps + state, distances, seed tiles of all episodes: three launches
+int field_preamble_batch(int E, peanut_goal* g0, const FieldBatchArgs& fa, const TravBatchArgs& ta, hipStream_t s) {
+  const int H = g0->H, W = g0->W, n = H * W, nt = g0->tiles_x * g0->tiles_y;
+  const dim3 tgrid((W + 31) / 32, (H + 7) / 8, E);
+  if (g0->rad <= TRAV_MAX_RAD) hipLaunchKernelGGL(goal_trav_batch_kernel, tgrid, dim3(256), 0, s, ta, H, W, g0->rad);
+  else hipLaunchKernelGGL(goal_trav_wide_batch_kernel, tgrid, dim3(256), 0, s, ta, H, W, g0->rad);
+  hipLaunchKernelGGL(fmm_flags_clear_batch_kernel, dim3((4 * nt + 255) / 256, E), dim3(256), 0, s, fa, 4 * nt);
+  hipLaunchKernelGGL(fmm_init_batch_kernel, dim3((n + 255) / 256, E), dim3(256), 0, s, fa, ta, H, W, g0->tiles_x, nt);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("peanut_goal_select_batch: ") + hipGetErrorString(e));
+}
+
+// enqueue_rounds for the batch: one launch per round over (tiles, E), one read-back of the [E][MAX_ROUNDS_PER_CHECK] counters
+template <bool SECOND>
+int enqueue_rounds_batch(GoalBatch* B, int E, peanut_goal* g0, FieldBatchArgs fa, unsigned int skip, int* cur, int batch, hipStream_t s) {
+  const int H = g0->H, W = g0->W, nt = g0->tiles_x * g0->tiles_y;
+  unsigned int* counters = (unsigned int*)B->counters.p;
+  const size_t bytes = (size_t)E * MAX_ROUNDS_PER_CHECK * sizeof(unsigned int);
+  fa.done = skip;
+  PEANUT_HIP_CHECK(hipMemsetAsync(counters, 0, bytes, s));
+  const bool local32 = opt(OPT_FMM_LOCAL32) != 0, blocked = opt(OPT_FMM_BLOCKED) != 0;
+  const int max_inner = (int)std::min<long long>(std::max<long long>(opt(OPT_FMM_INNER), 1), 1024);
+  for (int k = 0; k < batch; ++k) {
+#define PEANUT_FMM_LAUNCH(KERNEL, ...) \
+  hipLaunchKernelGGL(KERNEL, dim3(nt, E), dim3(1024), 0, s, fa, H, W, g0->tiles_x, g0->tiles_y, *cur, counters, k, ##__VA_ARGS__)
+    if (blocked) {
+      if (local32) PEANUT_FMM_LAUNCH((fmm_round_blocked_batch_kernel<SECOND, true>), max_inner);
+      else PEANUT_FMM_LAUNCH((fmm_round_blocked_batch_kernel<SECOND, false>), max_inner);
+    } else {
+      if (local32) PEANUT_FMM_LAUNCH((fmm_round_batch_kernel<SECOND, true>));
+      else PEANUT_FMM_LAUNCH((fmm_round_batch_kernel<SECOND, false>));
+    }
+#undef PEANUT_FMM_LAUNCH
+    *cur = (*cur + 1) % 3;
+  }
+  PEANUT_HIP_CHECK(hipMemcpyAsync(B->host_counters, counters, bytes, hipMemcpyDeviceToHost, s));
+  return 0;
+}
+
+inline int first_batch_of(int E, peanut_goal_t* const* g, unsigned int skip, int stage) {
+  int b = 4;
+  for (int e = 0; e < E; ++e)
+    if (!((skip >> e) & 1u)) b = std::max(b, first_batch(g[e], stage));
+  return b;
+}
+
+// run_stage for the batch.  done: the episodes that take no part (bits >= E are set); changed[e] = tiles changed over the stage
+template <bool SECOND>
+int run_stage_batch(GoalBatch* B, int E, peanut_goal_t* const* g, const FieldBatchArgs& fa, int stage, unsigned int done, int* cur,
+                    int* rounds_used, unsigned long long* changed, hipStream_t s, int enqueued = 0) {
+  const int max_rounds = 32 * (g[0]->tiles_x + g[0]->tiles_y) + 64;
+  int needed[GB] = {0};
+  for (int e = 0; e < E; ++e) changed[e] = 0;
+  unsigned int settled = done;
+  int batch = enqueued > 0 ? enqueued : first_batch_of(E, g, done, stage);
+  for (int round = 0; round < max_rounds; round += batch, batch = ROUNDS_PER_CHECK) {
+    if (!(round == 0 && enqueued > 0))
+      if (int rc = enqueue_rounds_batch<SECOND>(B, E, g[0], fa, settled, cur, batch, s)) return rc;
+    PEANUT_HIP_CHECK(hipStreamSynchronize(s));
+    *rounds_used += batch;
+    for (int e = 0; e < E; ++e) {
+      if ((settled >> e) & 1u) continue;
+      const unsigned int* host = B->host_counters + (size_t)e * MAX_ROUNDS_PER_CHECK;
+      for (int k = 0; k < batch; ++k) {
+        changed[e] += host[k];
+        if (host[k]) needed[e] = round + k + 1;
+      }
+      if (host[batch - 1] == 0) {
+        g[e]->round_hint[stage] = needed[e];
+        settled |= 1u << e;
+      }
+    }
+    if (settled == 0xffffffffu) return 0;
+  }
+  return fail(PEANUT_EHIP, "fmm: a relaxation stage of the batch did not settle within its round budget");
+}
+
+// begun_batch > 0: the preamble and that many stage-A rounds are already on `s` (begun_cur = the flag rotation after them)
+int solve_field_batch(GoalBatch* B, int E, peanut_goal_t* const* g, const FieldBatchArgs& fa, const TravBatchArgs& ta, hipStream_t s,
+                      int begun_batch, int begun_cur) {
+  const int n = g[0]->H * g[0]->W, nt = g[0]->tiles_x * g[0]->tiles_y;
+  int cur = 0, rounds = 0;
+  unsigned long long changed[GB];
+  unsigned int done = E >= 32 ? 0u : ~((1u << E) - 1u);
+  if (begun_batch > 0) {
+    cur = begun_cur;
+  } else if (int rc = field_preamble_batch(E, g[0], fa, ta, s)) {
+    return rc;
+  }
+  if (int rc = run_stage_batch<false>(B, E, g, fa, 0, done, &cur, &rounds, changed, s, begun_batch)) return rc;
+  for (int e = 0; e < E; ++e) { g[e]->last_passes = 0; g[e]->last_converged = false; }
+  const int max_passes = (int)std::min<long long>(std::max<long long>(opt(OPT_FMM_MAX_PASSES), 2), 64);
+  for (int pass = 0; pass < max_passes && done != 0xffffffffu; ++pass) {
+    FieldBatchArgs pa = fa;
+    pa.done = done;
+    if (pass == 0) cur = 0;
+    hipLaunchKernelGGL(fmm_pass_batch_kernel, dim3((n + 255) / 256, E), dim3(256), 0, s, pa, n, nt, pass == 0 ? 1 : 0, cur);
+    if (int rc = run_stage_batch<true>(B, E, g, fa, 1 + pass, done, &cur, &rounds, changed, s)) return rc;
+    for (int e = 0; e < E; ++e) {
+      if ((done >> e) & 1u) continue;
+      g[e]->last_passes = pass + 1;
+      if (pass > 0 && changed[e] == 0) { g[e]->last_converged = true; done |= 1u << e; }
+    }
+  }
+  for (int e = 0; e < E; ++e) g[e]->last_rounds = rounds;
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(PEANUT_EHIP, std::string("fmm: ") + hipGetErrorString(err));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int peanut_goal_select_begin_batch(int E, peanut_goal_t* const* g, const float* const* full_obstacle, const uint8_t* const* collision_map,
+                                   const uint8_t* const* visited_vis, const int* lmb, const int* loc_rc, void* stream) {
+  if (int rc = check_batch("peanut_goal_select_begin_batch", E, g, full_obstacle, lmb, loc_rc)) return rc;
+  peanut::OptionScope option_scope(&g[0]->opts);
+  if (int rc = ensure_batch(g[0])) return rc;
+  drain_all(E, g);
+  GoalBatch* B = g[0]->batch.get();
+  if (B->begun.on) (void)hipStreamSynchronize(B->side);      // (cannot be: a begun batch of this lead holds the lead; kept as a guard)
+  PEANUT_HIP_CHECK(hipEventRecord(B->ev_inputs, (hipStream_t)stream));
+  PEANUT_HIP_CHECK(hipStreamWaitEvent(B->side, B->ev_inputs, 0));
+  // as peanut_goal_select_begin: the handles are marked busy BEFORE the first enqueue (with no inputs yet, which match no select),
+  // and an enqueue that fails part-way lets the side stream run out before the error is returned
+  GoalBatch::Begun& b = B->begun;
+  b = GoalBatch::Begun{};
+  b.on = true; b.E = E;
+  for (int e = 0; e < E; ++e) { b.g[e] = g[e]; g[e]->begun_in = g[0]->batch; }
+  FieldBatchArgs fa;
+  TravBatchArgs ta;
+  fill_field_args(E, g, lmb, loc_rc, &fa, &ta, full_obstacle, collision_map, visited_vis);
+  int cur = 0, batch = 0;
+  int rc = field_preamble_batch(E, g[0], fa, ta, B->side);
+  if (!rc) { batch = first_batch_of(E, g, 0u, 0); rc = enqueue_rounds_batch<false>(B, E, g[0], fa, ~((E >= 32 ? 0u : (1u << E)) - 1u), &cur, batch, B->side); }
+  if (!rc && hipGetLastError() != hipSuccess) rc = fail(PEANUT_EHIP, "peanut_goal_select_begin_batch: launch failed");
+  if (rc) {
+    drain_batch_of(g[0]);
+    return rc;
+  }
+  for (int e = 0; e < E; ++e) {
+    b.obst[e] = full_obstacle[e]; b.col[e] = collision_map ? collision_map[e] : nullptr; b.vis[e] = visited_vis ? visited_vis[e] : nullptr;
+    for (int i = 0; i < 4; ++i) b.lmb[e][i] = lmb[4 * e + i];
+    b.loc[e][0] = loc_rc[2 * e]; b.loc[e][1] = loc_rc[2 * e + 1];
+  }
+  b.batch = batch; b.cur = cur;
+  return 0;
+}
+
+int peanut_goal_select_batch(int E, peanut_goal_t* const* g, const float* const* full_obstacle, const uint8_t* const* collision_map,
+                             const uint8_t* const* visited_vis, const int* lmb, const int* loc_rc, const float* const* target_pred,
+                             double dist_weight_temperature, int map_resolution, int* goal_rc_out, double* stats_out,
+                             double* const* dist_out, double* const* value_out, void* stream) {
+  if (int rc = check_batch("peanut_goal_select_batch", E, g, full_obstacle, lmb, loc_rc)) return rc;
+  if (!goal_rc_out) return fail(PEANUT_EINVAL, "peanut_goal_select_batch: null argument");
+  const int mode = dist_weight_temperature == -1 ? 1 : (dist_weight_temperature == 0 ? 2 : 0);
+  if (mode != 2) {
+    if (!target_pred) return fail(PEANUT_EINVAL, "peanut_goal_select_batch: target_pred is needed unless dist_weight_temperature == 0");
+    for (int e = 0; e < E; ++e)
+      if (!target_pred[e]) return fail(PEANUT_EINVAL, "peanut_goal_select_batch: target_pred is needed unless dist_weight_temperature == 0");
+  }
+  peanut::OptionScope option_scope(&g[0]->opts);
+  if (int rc = ensure_batch(g[0])) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  GoalBatch* B = g[0]->batch.get();
+  // a batch begun for these very handles, in this order, with these very inputs is taken over; anything else runs out first
+  bool aside = B->begun.on && B->begun.E == E && B->begun.batch > 0;
+  for (int e = 0; aside && e < E; ++e) {
+    const GoalBatch::Begun& b = B->begun;
+    aside = b.g[e] == g[e] && g[e]->begun_in.get() == B && !g[e]->begun.on && b.obst[e] == full_obstacle[e] &&
+            b.col[e] == (collision_map ? collision_map[e] : nullptr) && b.vis[e] == (visited_vis ? visited_vis[e] : nullptr) &&
+            b.lmb[e][0] == lmb[4 * e] && b.lmb[e][1] == lmb[4 * e + 1] && b.lmb[e][2] == lmb[4 * e + 2] && b.lmb[e][3] == lmb[4 * e + 3] &&
+            b.loc[e][0] == loc_rc[2 * e] && b.loc[e][1] == loc_rc[2 * e + 1];
+  }
+  FieldBatchArgs fa;
+  TravBatchArgs ta;
+  fill_field_args(E, g, lmb, loc_rc, &fa, &ta, full_obstacle, collision_map, visited_vis);
+  if (aside) {
+    const int begun_batch = B->begun.batch, begun_cur = B->begun.cur;
+    for (int e = 0; e < E; ++e) { g[e]->begun_in.reset(); B->begun.g[e] = nullptr; }
+    B->begun.on = false; B->begun.E = 0;
+    if (int rc = solve_field_batch(B, E, g, fa, ta, B->side, begun_batch, begun_cur)) {
+      (void)hipStreamSynchronize(B->side);      // `s` never joined the side stream: let it run out before the scratch is reused
+      return rc;
+    }
+    PEANUT_HIP_CHECK(hipEventRecord(B->ev_field, B->side));
+    PEANUT_HIP_CHECK(hipStreamWaitEvent(s, B->ev_field, 0));
+  } else {
+    drain_all(E, g);
+    if (int rc = solve_field_batch(B, E, g, fa, ta, s, 0, 0)) return rc;
+  }
+  const int lw = lmb[1] - lmb[0], lh = lmb[3] - lmb[2], n = lw * lh;
+  SelectBatchArgs sa{};
+  sa.res = (GoalResult*)B->results.p;
+  for (int e = 0; e < E; ++e) {
+    peanut_goal* h = g[e];
+    if (h->have_last && (h->last_lw != lw || h->last_lh != lh)) h->have_last = false;
+    sa.dist[e] = (const double*)h->dist.p; sa.target_pred[e] = target_pred ? target_pred[e] : nullptr;
+    sa.wt_new[e] = (double*)h->wt_new.p; sa.wt_last[e] = (double*)h->wt_last.p; sa.wt_part[e] = (double*)h->wt_part.p;
+    sa.sum[e] = (double*)h->sum.p; sa.partial[e] = (ArgMax*)h->partial.p;
+    sa.value[e] = value_out && value_out[e] ? value_out[e] : (double*)h->value.p;
+    sa.gx1[e] = lmb[4 * e]; sa.gy1[e] = lmb[4 * e + 2]; sa.have_last[e] = h->have_last ? 1 : 0;
+  }
+  const double temperature = dist_weight_temperature / (double)map_resolution;      // (:395)
+  const int nwt = (n + 255) / 256, nparts = std::min(1024, (n + 255) / 256);
+  PEANUT_HIP_CHECK(hipMemsetAsync(B->results.p, 0, (size_t)E * sizeof(GoalResult), s));
+  hipLaunchKernelGGL(goal_field_max_batch_kernel, dim3(256, E), dim3(256), 0, s, sa, g[0]->H * g[0]->W);
+  hipLaunchKernelGGL(goal_weight_batch_kernel, dim3(nwt, E), dim3(256), 0, s, sa, g[0]->W, lw, lh, temperature, mode == 2 ? 1 : 0);
+  hipLaunchKernelGGL(goal_sum_batch_kernel, dim3(1, E), dim3(256), 0, s, sa, nwt);
+  hipLaunchKernelGGL(goal_argmax_batch_kernel, dim3(nparts, E), dim3(256), 0, s, sa, mode, n);
+  hipLaunchKernelGGL(goal_argmax_final_batch_kernel, dim3(1, E), dim3(64), 0, s, sa, nparts, mode, n);
+  if (mode != 2) hipLaunchKernelGGL(goal_keep_batch_kernel, dim3(nwt, E), dim3(256), 0, s, sa, n);
+  PEANUT_HIP_CHECK(hipMemcpyAsync(B->host_results, B->results.p, (size_t)E * sizeof(GoalResult), hipMemcpyDeviceToHost, s));
+  if (dist_out)
+    for (int e = 0; e < E; ++e)
+      if (dist_out[e]) PEANUT_HIP_CHECK(hipMemcpyAsync(dist_out[e], g[e]->dist.p, (size_t)g[e]->H * g[e]->W * sizeof(double), hipMemcpyDeviceToDevice, s));
+  PEANUT_HIP_CHECK(hipStreamSynchronize(s));
+  for (int e = 0; e < E; ++e) {
+    const GoalResult& r = B->host_results[e];
+    if (r.idx[0] < 0 || r.idx[0] >= n) return fail(PEANUT_EHIP, "peanut_goal_select_batch: argmax outside the local window");
+    if (!r.idx[1] && mode != 2) { g[e]->last_lw = lw; g[e]->last_lh = lh; }
+    if (mode != 2) g[e]->have_last = true;      // (frontier mode neither uses nor replaces the last weights)
+    goal_rc_out[2 * e] = r.idx[0] / lh;
+    goal_rc_out[2 * e + 1] = r.idx[0] - goal_rc_out[2 * e] * lh;
+    if (stats_out) {
+      stats_out[4 * e] = r.val[0]; stats_out[4 * e + 1] = r.val[1]; stats_out[4 * e + 2] = r.idx[1];
+      stats_out[4 * e + 3] = g[e]->last_rounds;
+    }
+  }
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("peanut_goal_select_batch: ") + hipGetErrorString(err));
+}
+
 int peanut_goal_rounds(peanut_goal_t* g) { return g ? g->last_rounds : PEANUT_EINVAL; }
 int peanut_goal_passes(peanut_goal_t* g) { return g ? g->last_passes : PEANUT_EINVAL; }
 int peanut_goal_converged(peanut_goal_t* g) { return g ? (g->last_converged ? 1 : 0) : PEANUT_EINVAL; }
@@ -891,6 +1430,7 @@ int peanut_fmm_distance(peanut_goal_t* g, const uint8_t* traversible, const uint
   if (!goal_mask && (goal_r < 0 || goal_r >= g->H || goal_c < 0 || goal_c >= g->W))
     return fail(PEANUT_EINVAL, "peanut_fmm_distance: goal cell outside the map");
   hipStream_t s = (hipStream_t)stream;
+  drain_batch_of(g);
   if (g->begun.on) { PEANUT_HIP_CHECK(hipStreamSynchronize(g->side)); g->begun.on = false; }      // (an unfinished select_begin owns the scratch)
   if (int rc = solve_field(g, traversible, goal_mask, goal_mask && goal_r < 0 ? -1 : goal_r, goal_c, s)) return rc;
   const int n = g->H * g->W;
@@ -936,6 +1476,7 @@ int peanut_goal_select(peanut_goal_t* g, const float* full_obstacle, const uint8
   // initialisation and the first batch of stage-A rounds are already running on the handle's own stream, next to what the caller
   // enqueued on `s` since (the forward that produces target_pred); the rest follows there and `s` joins before the weights
   bool aside = false;
+  drain_batch_of(g);
   if (g->begun.on) {
     const peanut_goal::Begun& b = g->begun;
     aside = b.obst == full_obstacle && b.col == collision_map && b.vis == visited_vis && b.lmb[0] == gx1 && b.lmb[1] == gx2 &&

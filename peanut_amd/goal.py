@@ -180,6 +180,112 @@ class GeodesicSolver:
         return out
 
 
+MAX_BATCH = 16      # PEANUT_GOAL_MAX_BATCH (include/peanut_hip.h)
+
+
+def _ptrs(tensors):
+    """E optional tensors -> a C array of E device pointers (NULL for None)."""
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _check_batch(solvers, items):
+    solvers, items = list(solvers), list(items)
+    if not 1 <= len(solvers) <= MAX_BATCH:
+        raise ValueError(f"a goal batch holds 1..{MAX_BATCH} solvers, got {len(solvers)}")
+    if len(items) != len(solvers):
+        raise ValueError(f"{len(items)} items for {len(solvers)} solvers")
+    if len({id(s) for s in solvers}) != len(solvers):
+        raise ValueError("the same GeodesicSolver appears twice")
+    if len({str(s.device) for s in solvers}) != 1:
+        raise ValueError("the solvers of a batch live on one device")
+    return solvers, items
+
+
+def _batch_geometry(items):
+    E = len(items)
+    bounds = (C.c_int * (4 * E))(*[int(v) for it in items for v in it[3]])
+    locs = (C.c_int * (2 * E))(*[int(v) for it in items for v in it[4]])
+    return bounds, locs
+
+
+def select_begin_batch(solvers, items):
+    """``GeodesicSolver.select_begin`` for E solvers in one library call (``peanut_goal_select_begin_batch``): ``items`` = per
+    episode ``(full_obstacle, collision_map, visited_vis, lmb, loc_rc)``.  The fields of all E episodes start now, on one side
+    stream, beside what is enqueued after this call; the ``select_batch`` over the same solvers and inputs takes them over."""
+    solvers, items = _check_batch(solvers, items)
+    dev = solvers[0].device
+    conv = [(it[0].to(dev, torch.float32).contiguous(), _u8(it[1], dev), _u8(it[2], dev)) for it in items]
+    bounds, locs = _batch_geometry(items)
+    handles = (C.c_void_p * len(solvers))(*[s._h.value for s in solvers])
+    held = [getattr(s, "_begun", None) for s in solvers]      # (an unfinished begin: its buffers live until the library has let it run out)
+    for s in solvers:
+        s._begun = None
+    with torch.cuda.device(dev):
+        rc = solvers[0]._lib.peanut_goal_select_begin_batch(len(solvers), handles, _ptrs([c[0] for c in conv]), _ptrs([c[1] for c in conv]),
+                                                            _ptrs([c[2] for c in conv]), bounds, locs, _lib.current_stream_ptr(dev))
+    _lib.check(rc, "peanut_goal_select_begin_batch")
+    del held
+    # as select_begin: the converted buffers AND the originals stay referenced next to the idents (a freed temporary could hand its
+    # block to the next one, whose ident would then match with other contents)
+    for s, it, c in zip(solvers, items, conv):
+        inputs = (it[0], it[1], it[2])
+        s._begun = (tuple(_ident(t) for t in inputs), c, inputs)
+
+
+def select_batch(solvers, items, target_preds, dist_weight_temperature: float, map_resolution: int, want_dist: bool = False,
+                 want_value: bool = False):
+    """``GeodesicSolver.select`` for E solvers in the launches and synchronisations of ONE solve (``peanut_goal_select_batch``);
+    every episode gets the bits its own ``select`` gives.  ``target_preds``: E tensors (or None / E Nones with
+    ``dist_weight_temperature == 0``).  Returns the list of the E dicts ``select`` returns; ``rounds`` is the batch's."""
+    solvers, items = _check_batch(solvers, items)
+    E, dev = len(solvers), solvers[0].device
+    target_preds = [None] * E if target_preds is None else list(target_preds)
+    if len(target_preds) != E:
+        raise ValueError(f"{len(target_preds)} target_preds for {E} solvers")
+    tps = [None if t is None else t.to(dev, torch.float32).contiguous() for t in target_preds]
+    conv, held = [], []
+    for s, it in zip(solvers, items):
+        begun, s._begun = getattr(s, "_begun", None), None
+        held.append(begun)               # referenced until the C call has returned: the side stream may still read its buffers
+        if begun is not None and begun[0] == tuple(_ident(t) for t in (it[0], it[1], it[2])):
+            conv.append(begun[1])
+            s.begun_matches += 1
+        else:
+            obst = it[0].to(dev, torch.float32).contiguous()
+            if begun is not None and obst.data_ptr() == begun[1][0].data_ptr():
+                obst = obst.clone()      # same buffer, other contents: a copy makes the library drop the begun field (select)
+            conv.append((obst, _u8(it[1], dev), _u8(it[2], dev)))
+    for it, tp in zip(items, tps):
+        lw, lh = int(it[3][1] - it[3][0]), int(it[3][3] - it[3][2])
+        if tp is not None and tuple(tp.shape) != (lw, lh):
+            raise ValueError(f"target_pred must be [{lw},{lh}], got {tuple(tp.shape)}")
+    bounds, locs = _batch_geometry(items)
+    handles = (C.c_void_p * E)(*[s._h.value for s in solvers])
+    goal, stats = (C.c_int * (2 * E))(), (C.c_double * (4 * E))()
+    lw, lh = int(items[0][3][1] - items[0][3][0]), int(items[0][3][3] - items[0][3][2])
+    dists = [torch.empty((s.H, s.W), dtype=torch.float64, device=dev) for s in solvers] if want_dist else None
+    values = [torch.empty((lw, lh), dtype=torch.float64, device=dev) for _ in solvers] if want_value else None
+    with torch.cuda.device(dev):
+        rc = solvers[0]._lib.peanut_goal_select_batch(E, handles, _ptrs([c[0] for c in conv]), _ptrs([c[1] for c in conv]),
+                                                      _ptrs([c[2] for c in conv]), bounds, locs, _ptrs(tps),
+                                                      float(dist_weight_temperature), int(map_resolution), goal, stats,
+                                                      None if dists is None else _ptrs(dists), None if values is None else _ptrs(values),
+                                                      _lib.current_stream_ptr(dev))
+    _lib.check(rc, "peanut_goal_select_batch")
+    del held
+    out = []
+    for e, s in enumerate(solvers):
+        s._note_convergence()
+        res = dict(goal=(int(goal[2 * e]), int(goal[2 * e + 1])), value_max=float(stats[4 * e]), wt_sum=float(stats[4 * e + 1]),
+                   kept_last=bool(stats[4 * e + 2]), rounds=int(stats[4 * e + 3]), passes=s.passes, converged=s.converged)
+        if want_dist:
+            res["dist"] = dists[e]
+        if want_value:
+            res["value"] = values[e]
+        out.append(res)
+    return out
+
+
 class GoalSelector:
     """``update_global_goal`` with its cross-call state (agent_state.py:376-415)."""
 

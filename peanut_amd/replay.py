@@ -52,13 +52,14 @@ def run_episode(state: Agent_State, frames: Iterable[Dict], goal_cat: int,
 
 def run_episodes(states, episodes, goal_cats, detector=None,
                  on_step: Optional[Callable[[int, List[Agent_State], List[bool]], None]] = None,
-                 batch_predictions: bool = False) -> List[int]:
+                 batch_predictions: bool = False, batch_goals: bool = True) -> List[int]:
     """``run_episode`` for E episodes in lock-step on one device (``Agent_State_Group``): ``states`` E ``Agent_State``
     objects with equal mapping arguments, ``episodes`` E frame sequences in the formats of ``run_episode``, ``goal_cats`` E
     goal categories.  Per step the frames of the episodes still running are formatted, projected and marked as one batch;
     with a ``detector`` that has ``semantic``, they go through ONE ``detector.semantic(rgb[E].flip(-1), ..., goal_cats)``
     call.  Episodes may differ in length: a finished one drops out and the others go on.  ``on_step(i, active_states,
-    predicted)`` is called after every step.  Returns the number of predictions per episode."""
+    predicted)`` is called after every step.  ``batch_goals``: the episodes that select a goal on the same step do so in one batched
+    solve (``Agent_State_Group``; the same bits as one by one).  Returns the number of predictions per episode."""
     import torch
     from .agent_helper import preprocess_obs_batch
     from .agent_state import Agent_State_Group
@@ -66,7 +67,7 @@ def run_episodes(states, episodes, goal_cats, detector=None,
     iters = [iter(ep) for ep in episodes]
     if not (len(states) == len(iters) == len(goal_cats)):
         raise ValueError(f"{len(states)} states, {len(iters)} episodes and {len(goal_cats)} goal categories")
-    group = Agent_State_Group(states, batch_predictions=batch_predictions)
+    group = Agent_State_Group(states, batch_predictions=batch_predictions, batch_goals=batch_goals)
     args = states[0].args
     for s in states:
         s.reset()

@@ -9,7 +9,14 @@ the two sides alternating (A B A B A B: three repeats each, the spread of the th
       of tools/bench_pipeline.py, 720 x 720 prediction + goal selection): E sequential `run_episode` calls against one
       `run_episodes`, steps/s/GPU summed over the episodes.
 
-    python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace]
+  (c) goal selection alone: E solvers on E different 960 x 960 maps (`goal`: the pipeline's synthetic episodes after 24 frames,
+      whose agent stands inside an obstacle so that the field ends at once; `goal_mazes`: seeded wall mazes the front crosses): E
+      `GeodesicSolver.select` calls against one `goal.select_batch`, with and without the preceding begin, milliseconds per
+      step of E episodes, wall clock around calls that end in their own synchronise; and the pipeline of (b) with
+      `batch_goals` off as a third column.  In a tree whose package has no `select_batch` (an older commit, for a side-by-side
+      run of its library) the sequential sides alone are measured.
+
+    python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only]
 
 writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
 of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
@@ -30,6 +37,7 @@ for p in (ROOT, os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 BATCHES = (1, 2, 4, 8)
+GOAL_BATCHES = (1, 2, 4, 8, 16)
 
 
 def _stage2_obs(E, dev, seed=0):
@@ -143,8 +151,9 @@ def forward_only(dev, steps=2000, repeats=3):
     return out
 
 
-def pipeline(dev, frames=40, repeats=3):
+def pipeline(dev, frames=40, repeats=3, batches=BATCHES):
     import gc
+    import inspect
 
     from bench_pipeline import synth_episode
     from peanut_amd.agent_state import Agent_State, default_args
@@ -157,7 +166,7 @@ def pipeline(dev, frames=40, repeats=3):
     model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
     rcfg = RcnnCfg(score_thresh_test=0.5)
     det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
-    emax = max(BATCHES)
+    emax = max(batches)
     eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
     for ep in eps:
         for fr in ep:
@@ -166,7 +175,7 @@ def pipeline(dev, frames=40, repeats=3):
     seq = [Agent_State(args, prediction_model=model) for _ in range(emax)]
     lock = [Agent_State(args, prediction_model=model) for _ in range(emax)]
     out = {}
-    for E in BATCHES:
+    for E in batches:
         goals = [3] * E
 
         def sequential():
@@ -174,13 +183,19 @@ def pipeline(dev, frames=40, repeats=3):
 
         def lockstep():
             return sum(run_episodes(lock[:E], eps[:E], goals, detector=det))
+
+        def lockstep_single_goals():
+            return sum(run_episodes(lock[:E], eps[:E], goals, detector=det, batch_goals=False))
+        sides = [("sequential", sequential), ("lockstep", lockstep)]
+        if "batch_goals" in inspect.signature(run_episodes).parameters:
+            sides.append(("lockstep_single_goals", lockstep_single_goals))
         run_episode(seq[0], eps[0][:12], goal_cat=3, detector=det)            # warm-up: plans and workspaces of both batch sizes
         run_episodes(lock[:E], [ep[:12] for ep in eps[:E]], goals, detector=det)
         gc.collect()
-        t = {"sequential": [], "lockstep": []}
+        t = {name: [] for name, _ in sides}
         preds = {}
         for _ in range(repeats):
-            for name, fn in (("sequential", sequential), ("lockstep", lockstep)):
+            for name, fn in sides:
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 preds[name] = fn()
@@ -189,8 +204,181 @@ def pipeline(dev, frames=40, repeats=3):
         out[str(E)] = {"sequential_steps_per_s": _spread(t["sequential"]), "lockstep_steps_per_s": _spread(t["lockstep"]),
                        "speedup_median": round(_spread(t["lockstep"])["median"] / _spread(t["sequential"])["median"], 3),
                        "predictions": preds}
+        if "lockstep_single_goals" in t:
+            out[str(E)]["lockstep_single_goals_steps_per_s"] = _spread(t["lockstep_single_goals"])
         print(f"pipeline, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
     return out
+
+
+def _goal_inputs(dev, n, frames=24, cache=None):
+    """The goal-selection inputs of n episodes after `frames` frames of the pipeline's synthetic episodes: per episode
+    (full_obstacle, collision_map, visited_vis, lmb, loc_rc) in the library's formats, and target_pred.  `cache`: a file to keep
+    them in between processes that must see the same inputs."""
+    if cache and os.path.exists(cache):
+        items, tps = torch.load(cache)
+        return [tuple(x.to(dev) if isinstance(x, torch.Tensor) else x for x in it) for it in items], [t.to(dev) for t in tps]
+    from bench_pipeline import synth_episode
+    from peanut_amd import goal as G
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episode
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    items, tps = [], []
+    for e in range(n):
+        ep = synth_episode(1000 + e, frames, dev)
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+        st = Agent_State(args, prediction_model=model)
+        run_episode(st, ep, goal_cat=3, detector=det)
+        st.full_map[:, st.lmb[0]:st.lmb[1], st.lmb[2]:st.lmb[3]] = st.local_map
+        items.append((st.full_map[0].clone(), G._u8(st.collision_map, dev).clone(), G._u8(st.visited_vis, dev).clone(),
+                      tuple(int(v) for v in st.lmb), (int(st.loc_r), int(st.loc_c))))
+        tps.append(st.target_pred.float().clone())
+    if cache:
+        torch.save(([tuple(x.cpu() if isinstance(x, torch.Tensor) else x for x in it) for it in items], [t.cpu() for t in tps]), cache)
+    return items, tps
+
+
+def _maze_inputs(dev, n, size=960, window=480):
+    """n seeded wall mazes in which the front crosses the whole map (the synthetic episodes' agent stands inside an obstacle:
+    their fields end at once), agent cells and windows of one size at different places."""
+    import numpy as np
+    items, tps = [], []
+    g = torch.Generator().manual_seed(0)
+    for e in range(n):
+        rng = np.random.RandomState(100 + e)
+        ob = np.zeros((size, size), np.float32)
+        for _ in range(int(0.012 * size * size / 20)):
+            r, c, k = rng.randint(0, size), rng.randint(0, size), rng.randint(10, 60)
+            if rng.rand() < 0.5:
+                ob[r:r + 2, c:c + k] = 1
+            else:
+                ob[r:r + k, c:c + 2] = 1
+        o = (size - window) // 2 + 10 * (e % 5) - 20
+        loc = (200 + 7 * e, 260 - 5 * e)
+        ob[o + loc[0] - 8:o + loc[0] + 9, o + loc[1] - 8:o + loc[1] + 9] = 0
+        z = torch.zeros((size, size), dtype=torch.uint8, device=dev)
+        items.append((torch.from_numpy(ob).to(dev), z, z.clone(), (o, o + window, o, o + window), loc))
+        tps.append(torch.rand((window, window), generator=g).to(dev))
+    return items, tps
+
+
+def goal(dev, calls=10, repeats=3, cache=None, col_rad=None, mazes=False):
+    from peanut_amd import goal as G
+    from peanut_amd.agent_state import default_args
+    args = default_args()
+    rad = int(args.col_rad) if col_rad is None else col_rad
+    T, res = float(getattr(args, "dist_weight_temperature", 500)), int(args.map_resolution)
+    items, tps = _maze_inputs(dev, max(GOAL_BATCHES)) if mazes else _goal_inputs(dev, max(GOAL_BATCHES), cache=cache)
+    H, W = items[0][0].shape
+    has_batch = hasattr(G, "select_batch")
+    out = {}
+    for E in GOAL_BATCHES:
+        seq = [G.GeodesicSolver(H, W, rad, device=dev) for _ in range(E)]
+        bat = [G.GeodesicSolver(H, W, rad, device=dev) for _ in range(E)]
+        last = {}
+
+        def sequential(n):
+            for _ in range(n):
+                last["sequential"] = [s.select(*it, tp, T, res)["goal"] for s, it, tp in zip(seq, items, tps)]
+
+        def sequential_begun(n):
+            for _ in range(n):
+                for s, it in zip(seq, items):
+                    s.select_begin(*it)
+                last["sequential_begun"] = [s.select(*it, tp, T, res)["goal"] for s, it, tp in zip(seq, items, tps)]
+
+        def batch(n):
+            for _ in range(n):
+                last["batch"] = [r["goal"] for r in G.select_batch(bat, items[:E], tps[:E], T, res)]
+
+        def batch_begun(n):
+            for _ in range(n):
+                G.select_begin_batch(bat, items[:E])
+                last["batch_begun"] = [r["goal"] for r in G.select_batch(bat, items[:E], tps[:E], T, res)]
+        sides = [("sequential", sequential), ("sequential_begun", sequential_begun)]
+        if has_batch:
+            sides += [("batch", batch), ("batch_begun", batch_begun)]
+        for _, fn in sides:
+            fn(3)
+        t = {name: [] for name, _ in sides}
+        for _ in range(repeats):
+            for name, fn in sides:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(calls)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / calls * 1e3)
+        out[str(E)] = {name + "_ms_per_step": _spread(v) for name, v in t.items()}
+        out[str(E)]["passes"] = [s.passes for s in seq]
+        out[str(E)]["rounds_sequential"] = [s.rounds for s in seq]
+        if has_batch:
+            out[str(E)]["rounds_batch"] = bat[0].rounds
+            out[str(E)]["goals_equal"] = bool(last["sequential"] == last["batch"] == last["batch_begun"])
+            out[str(E)]["speedup_median"] = round(_spread(t["sequential"])["median"] / _spread(t["batch"])["median"], 3)
+        print(f"goal{' (mazes)' if mazes else ''}, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
+    return out
+
+
+def goal_trace_child(dev, E, cache=None):
+    """What the profiler watches: E solvers on E copies of ONE map (they settle together, so the last rounds of a stage wake no
+    tile of any episode), two warm-up select_batch calls, a pause, one select_batch."""
+    from peanut_amd import goal as G
+    from peanut_amd.agent_state import default_args
+    args = default_args()
+    items, tps = _maze_inputs(dev, 1)
+    H, W = items[0][0].shape
+    sols = [G.GeodesicSolver(H, W, int(args.col_rad), device=dev) for _ in range(E)]
+    its = [tuple(x.clone() if isinstance(x, torch.Tensor) else x for x in items[0]) for _ in range(E)]
+    for _ in range(2):
+        G.select_batch(sols, its, [tps[0]] * E, 500.0, int(args.map_resolution))
+    torch.cuda.synchronize()
+    time.sleep(0.3)
+    r = G.select_batch(sols, its, [tps[0]] * E, 500.0, int(args.map_resolution))
+    torch.cuda.synchronize()
+    print(json.dumps({"E": E, "rounds": r[0]["rounds"], "passes": r[0]["passes"]}), flush=True)
+
+
+def goal_trace(out_dir, cache=None):
+    """Per E = 1, 8, 16 one profiler run of `goal_trace_child`: round-kernel dispatches of the last select_batch against the rounds
+    it reports, and the duration of a round in which no tile is awake (the shortest dispatches of the round kernel)."""
+    res = {}
+    for E in (1, 8, 16):
+        tdir = os.path.join(out_dir, f"goal_trace_tmp_{E}")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", tdir, "--", sys.executable, os.path.abspath(__file__),
+               "--goal-trace-child", str(E)] + (["--goal-inputs", cache] if cache else [])
+        try:
+            r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=240, text=True)
+        except (OSError, subprocess.TimeoutExpired) as e:
+            res[str(E)] = {"error": f"rocprofv3 did not run: {e}"}
+            continue
+        dbs = glob.glob(os.path.join(tdir, "**", "*.db"), recursive=True)
+        if r.returncode != 0 or not dbs:
+            res[str(E)] = {"error": f"rocprofv3 exit {r.returncode}, {len(dbs)} databases", "tail": r.stdout[-600:]}
+            continue
+        said = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith('{"E"')]
+        rows = sqlite3.connect(dbs[0]).execute("select name, start, end from kernels order by start").fetchall()
+        cut = max(range(1, len(rows)), key=lambda i: rows[i][1] - rows[i - 1][2])       # the pause
+        ks = rows[cut:]
+        rk = sorted((k[2] - k[1]) / 1e3 for k in ks if "fmm_round" in k[0])
+        busy = sum(k[2] - k[1] for k in ks) / 1e3
+        res[str(E)] = {"reported_rounds": said[-1]["rounds"] if said else None, "passes": said[-1]["passes"] if said else None,
+                       "round_kernel_dispatches": len(rk), "kernels": len(ks),
+                       "round_us_shortest_five": [round(x, 2) for x in rk[:5]], "round_us_median": round(rk[len(rk) // 2], 2) if rk else None,
+                       "round_kernel_us_total": round(sum(rk), 1), "all_kernel_us": round(busy, 1),
+                       "span_us": round((ks[-1][2] - ks[0][1]) / 1e3, 1)}
+        import shutil
+        shutil.rmtree(tdir, ignore_errors=True)
+    res["note"] = ("one select_batch over E copies of one map, under the profiler (every launch is slower: the us show the split, not "
+                   "the rate); the shortest round dispatches are rounds in which no tile of any episode is awake")
+    return res
 
 
 def trace_child(dev, E=8, steps=50):
@@ -247,20 +435,41 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lockstep"))
     ap.add_argument("--no-pipeline", action="store_true")
     ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--goal-only", action="store_true", help="the goal section alone")
+    ap.add_argument("--pipeline-only", action="store_true", help="the pipeline section alone")
+    ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
+    ap.add_argument("--goal-inputs", default=None, help="file that keeps the goal section's inputs between processes")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--goal-trace-child", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args()
     dev = torch.device("cuda", torch.cuda.current_device())
     if a.trace_child:
         trace_child(dev)
         return
+    if a.goal_trace_child:
+        goal_trace_child(dev, a.goal_trace_child, cache=a.goal_inputs)
+        return
     os.makedirs(a.out, exist_ok=True)
     rec = {"device": torch.cuda.get_device_name(dev), "batches": list(BATCHES),
-           "method": "one process; per E the two sides alternate, three repeats each; spread = min / median / max of the three",
-           "forward_only": forward_only(dev), "stage2": stage2(dev)}
-    if not a.no_pipeline:
-        rec["pipeline"] = pipeline(dev)
-    if not a.no_trace:
-        rec["trace"] = trace(a.out)
+           "method": "one process; per E the two sides alternate, three repeats each; spread = min / median / max of the three"}
+    pb = tuple(int(b) for b in a.pipeline_batches.split(","))
+    if a.goal_only:
+        rec["goal"] = goal(dev, cache=a.goal_inputs)
+        rec["goal_mazes"] = goal(dev, mazes=True)
+        if not a.no_trace:
+            rec["goal_trace"] = goal_trace(a.out)
+    elif a.pipeline_only:
+        rec["pipeline"] = pipeline(dev, batches=pb)
+    else:
+        rec["forward_only"] = forward_only(dev)
+        rec["stage2"] = stage2(dev)
+        rec["goal"] = goal(dev, cache=a.goal_inputs)
+        rec["goal_mazes"] = goal(dev, mazes=True)
+        if not a.no_pipeline:
+            rec["pipeline"] = pipeline(dev, batches=pb)
+        if not a.no_trace:
+            rec["trace"] = trace(a.out)
+            rec["goal_trace"] = goal_trace(a.out)
     with open(os.path.join(a.out, "lockstep.json"), "w") as f:
         json.dump(rec, f, indent=1)
         f.write("\n")
