@@ -238,11 +238,15 @@ def batched_nms(boxes, scores, cats, thr):
     return order[keep]
 
 
-def rpn_proposals(obj: List[torch.Tensor], deltas: List[torch.Tensor], image_hw, cfg: RcnnCfg):
-    """obj[l] [B,A,h,w], deltas[l] [B,4A,h,w] (NCHW as the modules emit them) -> per image (boxes, logits)."""
+def rpn_proposals(obj: List[torch.Tensor], deltas: List[torch.Tensor], image_hw, cfg: RcnnCfg, stages: dict = None):
+    """obj[l] [B,A,h,w], deltas[l] [B,4A,h,w] (NCHW as the modules emit them) -> per image (boxes, logits).
+    Tie rule (the project's own; detectron2 leaves it to ``torch.sort`` / ``topk``): among equal logits the lower flat index
+    (y, x, a) of a level comes first, in the per-level top-k and -- level after level -- in the NMS order (stable sorts).
+    ``stages``: a dict that receives ``sel_idx`` / ``sel_score`` ([B, sum of the levels' k]: the per-level selection, level
+    after level, before the validity tests) and ``nvalid`` (per image: candidates that pass them, i.e. that enter the NMS)."""
     B = obj[0].shape[0]
     strides = [4, 8, 16, 32, 64]
-    sc, pr, lv = [], [], []
+    sc, pr, lv, sel = [], [], [], []
     for l, (o, d) in enumerate(zip(obj, deltas)):
         h, w = o.shape[2:]
         A = o.shape[1]
@@ -252,11 +256,14 @@ def rpn_proposals(obj: List[torch.Tensor], deltas: List[torch.Tensor], image_hw,
         props = apply_deltas(dl.reshape(-1, 4), anchors.unsqueeze(0).expand(B, -1, -1).reshape(-1, 4),
                              cfg.rpn_bbox_weights).view(B, -1, 4)
         k = min(logits.shape[1], cfg.rpn_pre_nms_topk)
-        s, idx = logits.sort(descending=True, dim=1)
+        s, idx = logits.sort(descending=True, dim=1, stable=True)
+        sel.append(idx[:, :k])
         sc.append(s[:, :k])
         pr.append(props[torch.arange(B)[:, None], idx[:, :k]])
         lv.append(torch.full((k,), l, dtype=torch.int64))
     sc, pr, lv = torch.cat(sc, 1), torch.cat(pr, 1), torch.cat(lv, 0)
+    if stages is not None:
+        stages.update(sel_idx=torch.cat(sel, 1), sel_score=sc.clone(), nvalid=[])
     out = []
     for n in range(B):
         boxes, scores, lvl = pr[n], sc[n], lv
@@ -265,6 +272,8 @@ def rpn_proposals(obj: List[torch.Tensor], deltas: List[torch.Tensor], image_hw,
         boxes = clip_boxes(boxes, image_hw)
         ne = ((boxes[:, 2] - boxes[:, 0]) > 0) & ((boxes[:, 3] - boxes[:, 1]) > 0)
         boxes, scores, lvl = boxes[ne], scores[ne], lvl[ne]
+        if stages is not None:
+            stages["nvalid"].append(len(boxes))
         keep = batched_nms(boxes, scores, lvl, cfg.rpn_nms_thresh)[:cfg.rpn_post_nms_topk]
         out.append((boxes[keep], scores[keep]))
     return out
@@ -413,8 +422,11 @@ def box_head(sd, feats: torch.Tensor):
     return scores, deltas
 
 
-def fast_rcnn_inference_single_image(boxes, scores, image_hw, cfg: RcnnCfg):
-    """boxes [R, K*4] (decoded), scores [R, K+1] (softmax) -> (boxes [n,4], scores [n], classes [n])."""
+def fast_rcnn_inference_single_image(boxes, scores, image_hw, cfg: RcnnCfg, stages: dict = None):
+    """boxes [R, K*4] (decoded), scores [R, K+1] (softmax) -> (boxes [n,4], scores [n], classes [n]).
+    Tie rule (the project's own; detectron2 leaves it to ``torch.sort`` inside batched_nms): among equal scores the lower flat
+    candidate index (proposal * K + class) comes first -- in the NMS order and therefore in the detections_per_image cut.
+    ``stages``: a dict whose list ``n_candidates`` receives the number of class candidates above the score threshold."""
     valid = torch.isfinite(boxes).all(1) & torch.isfinite(scores).all(1)
     boxes, scores = boxes[valid], scores[valid]
     scores = scores[:, :-1]
@@ -423,6 +435,8 @@ def fast_rcnn_inference_single_image(boxes, scores, image_hw, cfg: RcnnCfg):
     mask = scores > cfg.score_thresh_test
     inds = mask.nonzero()
     boxes, scores = boxes[mask], scores[mask]
+    if stages is not None:
+        stages.setdefault("n_candidates", []).append(len(scores))
     keep = batched_nms(boxes, scores, inds[:, 1], cfg.nms_thresh_test)[:cfg.detections_per_image]
     return boxes[keep], scores[keep], inds[keep][:, 1]
 
@@ -456,22 +470,23 @@ def paste_masks(masks: torch.Tensor, boxes: torch.Tensor, hw, thr: float) -> tor
     return paste_values(masks, boxes, hw) >= thr
 
 
-def inference(sd, img_bgr_u8: torch.Tensor, cfg: RcnnCfg, vectorised: bool = False):
+def inference(sd, img_bgr_u8: torch.Tensor, cfg: RcnnCfg, vectorised: bool = False, stages: dict = None):
     """GeneralizedRCNN.inference + detector_postprocess for a batch; list of dicts (pred_boxes, scores,
     pred_classes, pred_masks bool [n,H,W]) at the ORIGINAL image resolution.  ``vectorised``: ROIAlign through
-    ``roi_align_vec`` (same values; needed at the full 1000 proposals per image)."""
+    ``roi_align_vec`` (same values; needed at the full 1000 proposals per image).  ``stages``: see ``rpn_proposals``;
+    also receives ``n_candidates`` (per image: class candidates above the score threshold)."""
     B, H, W, _ = img_bgr_u8.shape
     nh, nw = resized_hw(H, W, cfg)
     pyr, obj, deltas = forward_front(sd, img_bgr_u8, cfg)
     results = []
     with torch.no_grad():
-        props = rpn_proposals(obj, deltas, (nh, nw), cfg)
+        props = rpn_proposals(obj, deltas, (nh, nw), cfg, stages)
         for n in range(B):
             pb = props[n][0]
             rois = torch.cat([torch.full((len(pb), 1), float(n)), pb], 1)
             scores, dl = box_head(sd, roi_pool(pyr, rois, cfg.box_pooler_resolution, vectorised))
             boxes = apply_deltas(dl, pb, cfg.roi_bbox_weights)
-            b, s, c = fast_rcnn_inference_single_image(boxes, F.softmax(scores, dim=-1), (nh, nw), cfg)
+            b, s, c = fast_rcnn_inference_single_image(boxes, F.softmax(scores, dim=-1), (nh, nw), cfg, stages)
             rois = torch.cat([torch.full((len(b), 1), float(n)), b], 1)
             logits = mask_head(sd, roi_pool(pyr, rois, cfg.mask_pooler_resolution, vectorised), cfg)
             probs = logits[torch.arange(len(b)), c].sigmoid() if len(b) else logits[:, 0]

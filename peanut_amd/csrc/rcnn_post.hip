@@ -36,6 +36,10 @@ constexpr int kLevels = 5;
 constexpr int kMaxAnchors = 8;
 constexpr float kScaleClamp = 4.135166556742356f;   // log(1000 / 16), Box2BoxTransform
 
+// Order-preserving bits of a float: a < b  =>  ord_key(a) < ord_key(b); a NaN with the sign bit clear ranks above +inf (first in
+// a descending sort, as in torch's).  The key orders BITS: -0.0f ranks below +0.0f, where torch compares them equal.  A logit
+// reaches the selection from a conv epilogue (+0 accumulator plus products plus bias), which does not produce -0.0 (zero weights
+// with bias -0.0 give +0.0 on both sides), so the difference cannot show; the selection is not changed for it.
 __device__ __forceinline__ unsigned ord_key(float f) {
   const unsigned u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);

@@ -159,7 +159,10 @@ def make_seeded_rcnn_state_dict(cfg: RcnnCfg = RcnnCfg(), seed: int = 0) -> "Ord
             if "bbox_pred" in key or "anchor" in key:
                 std *= 0.2             # small box refinements
             if "cls_score" in key:
-                std *= 0.35            # keep the softmax un-saturated: distinct scores, no ties in the sorts
+                # keep the softmax un-saturated: distinct scores, no ties in the sorts.  (The tied and saturated regimes -- a
+                # trained detector's normal case -- are tested with crafted heads: tests/rcnn_cases.py,
+                # tests/test_rcnn_selection_gpu.py.)
+                std *= 0.35
             if "mask_head.predictor" in key:
                 std *= 2.0             # mask logits of both signs
             sd[key] = torch.randn(shape, generator=g) * std

@@ -169,3 +169,53 @@ def test_pil_resize_restatement_is_pinned_on_pillow(golden_dir):
     for (h, w, nh, nw) in ((480, 640, 800, 1067), (600, 900, 400, 600)):
         img = rng.randint(0, 256, (h, w, 3), dtype=np.uint8)
         assert np.array_equal(rcnn_ref.pil_resize_bilinear_u8(img, nh, nw), np.asarray(Image.fromarray(img).resize((nw, nh), Image.BILINEAR)))
+
+
+def test_crafted_selection_cases_have_the_properties_they_are_named_for():
+    """tests/rcnn_cases.py crafts the state dicts that tests/test_rcnn_selection_gpu.py runs through the HIP detector.  From the
+    oracle alone: each case has the ties / full capacities / empty lists it exists for, so that no GPU case can pass vacuously
+    (a seed or generator change that breaks one shows here)."""
+    from rcnn_cases import CASES, level_ks, make_case, oracle_run
+    assert len(CASES) == 11
+    out = {name: oracle_run(name) for name in CASES}
+    # the top-k cut falls inside a run of equal logits on at least three levels (on four here), and takes only part of the run
+    for name in ("rpn_ties", "rpn_ties_anchors", "full_capacities"):
+        cfg, sd, img = make_case(name)
+        obj = rcnn_ref.forward_front(sd, img, cfg)[1]
+        cut = 0
+        for (off, k, n), o in zip(level_ks(cfg, img.shape[1], img.shape[2]), obj):
+            logits = o.permute(0, 2, 3, 1).flatten(1)
+            assert logits.shape[1] == n
+            assert set(logits.unique().tolist()) == {0.5, 2.0, -1.0}             # 0 * x + bias = bias, bit for bit
+            s = logits.sort(descending=True, dim=1, stable=True)[0]
+            cut += int(k < n and bool((s[:, k - 1] == s[:, k]).all()))
+            assert torch.equal(out[name][1]["sel_score"][:, off:off + k], s[:, :k])
+        assert cut >= 3, (name, cut)
+    for name in ("rpn_ties", "rpn_ties_anchors"):
+        assert all(len(r["proposals"]) == 40 for r in out[name][0])
+    ref, st = out["all_tied"]
+    assert st["n_candidates"] == [360, 360] and all(len(r["scores"]) == 10 and len(r["scores"].unique()) == 1 for r in ref)
+    assert all(bool((r["scores"] == 1.0).all()) and r["pred_classes"].tolist() == [3] * 10 for r in out["saturated"][0])
+    for name in ("saturated_real_heads", "full_saturated_real_heads"):
+        sc = torch.cat([r["scores"] for r in out[name][0]])
+        assert len(sc) > 0 and int((sc == 1.0).sum()) * 2 >= len(sc), name
+    cfg = make_case("select_then_filter")[0]
+    assert all(0 < len(r["proposals"]) < cfg.rpn_post_nms_topk // 2 for r in out["select_then_filter"][0])
+    assert all(n < 60 for n in out["select_then_filter"][1]["nvalid"])            # the three fine levels lost all their candidates
+    assert all(len(r["proposals"]) == 0 and len(r["scores"]) == 0 for r in out["no_proposal"][0]) and out["no_proposal"][1]["nvalid"] == [0, 0]
+    assert all(len(r["proposals"]) == 5 and len(r["scores"]) > 0 for r in out["clamp"][0])
+    ref, st = out["nan_objectness"]
+    assert bool(st["sel_score"][:, 0].isnan().all()) and all(0 < len(r["proposals"]) < 40 for r in ref)
+    ref, st = out["full_capacities"]
+    assert len(ref[0]["proposals"]) == 1000 and st["n_candidates"] == [1000 * 9] and len(ref[0]["scores"]) == 100
+    assert sorted(set(ref[0]["pred_classes"].tolist())) == list(range(9)) and len(ref[0]["scores"].unique()) == 1
+    # ... and with the level's logits cut into eight slices (rcnn_topk_slice=300 at this size: ceil(n / 8) logits each), the winners
+    # of some level come from at least two slices without reaching the last one: the cut among equal logits falls in a middle slice
+    cfg, _, img = make_case("full_capacities")
+    middle = 0
+    for off, k, n in level_ks(cfg, img.shape[1], img.shape[2]):
+        slices = (st["sel_idx"][0, off:off + k] // -(-n // 8)).unique().tolist()
+        middle += int(len(slices) >= 2 and 7 not in slices)
+    assert middle >= 1
+    ref, st = out["full_saturated_real_heads"]
+    assert len(ref[0]["proposals"]) == 1000 and len(ref[0]["scores"]) == 100

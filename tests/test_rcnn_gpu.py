@@ -55,10 +55,8 @@ def test_preprocess_geometry_of_the_agent_frame():
 # the chain as a whole.
 # ---------------------------------------------------------------------------------------------------------
 def _small_cfg(**kw):
-    from peanut_amd.rcnn_weights import RcnnCfg
-    base = dict(depth=50, min_size=128, max_size=256, rpn_pre_nms_topk=60, rpn_post_nms_topk=40, detections_per_image=10)
-    base.update(kw)
-    return RcnnCfg(**base)
+    from rcnn_cases import small_cfg      # one definition, shared with tests/test_rcnn_selection_gpu.py
+    return small_cfg(**kw)
 
 
 def _nhwc(t):
@@ -92,11 +90,9 @@ def test_front_end_in_the_emulated_modes(precision, tol):
 def small_net():
     from oracle import rcnn_ref
     from rcnn_glue import GlueMaskRCNN as MaskRCNN      # the product class + the torch-glue stage methods (tests/rcnn_glue.py)
-    from peanut_amd.rcnn_weights import make_seeded_rcnn_state_dict, resized_hw
-    cfg = _small_cfg()
-    sd = make_seeded_rcnn_state_dict(cfg, seed=7)
-    g = torch.Generator().manual_seed(11)
-    img = torch.randint(0, 256, (2, 96, 128, 3), generator=g, dtype=torch.uint8)
+    from peanut_amd.rcnn_weights import resized_hw
+    from rcnn_cases import small_inputs
+    cfg, sd, img = small_inputs()
     pyr, obj, dl = rcnn_ref.forward_front(sd, img, cfg)
     return dict(cfg=cfg, sd=sd, img=img, pyr=pyr, obj=obj, dl=dl, hw=resized_hw(96, 128, cfg), net=MaskRCNN(cfg, sd))
 
@@ -116,6 +112,26 @@ def test_nms_bit_exact():
             assert torch.equal(ref, got), (n, ncat, thr)
         got = nms_keep(boxes.cuda(), None, 0.5).cpu()
         assert torch.equal(rcnn_ref.nms_sorted(boxes, torch.zeros(n, dtype=torch.int64), 0.5), got)
+    # hand-made lists: the decisions a random list never meets
+    zeros = lambda n: torch.zeros(n, dtype=torch.int64)      # noqa: E731
+    dup = torch.tensor([[3.0, 4.0, 30.0, 20.0]]).repeat(5, 1)                              # exact duplicates: IoU = 1
+    assert nms_keep(dup.cuda(), zeros(5).cuda(), 0.7).cpu().tolist() == rcnn_ref.nms_sorted(dup, zeros(5), 0.7).tolist() == [True] + [False] * 4
+    assert nms_keep(dup.cuda(), torch.arange(5).cuda(), 0.7).cpu().tolist() == [True] * 5   # ... of five categories: all kept
+    empty = torch.tensor([[5.0, 5.0, 5.0, 5.0], [5.0, 5.0, 5.0, 5.0], [5.0, 5.0, 9.0, 5.0], [0.0, 0.0, 9.0, 9.0]])   # zero area: 0 / 0 = NaN,
+    for thr in (0.0, 0.5):                                                                   # and NaN > thr is false on both sides
+        assert nms_keep(empty.cuda(), zeros(4).cuda(), thr).cpu().tolist() == rcnn_ref.nms_sorted(empty, zeros(4), thr).tolist() == [True] * 4
+    pair = torch.tensor([[0.0, 0.0, 2.0, 1.0], [1.0, 0.0, 3.0, 1.0]])                      # IoU = 1 / 3, computed the oracle's way in fp32
+    third = float(torch.tensor(1.0) / torch.tensor(3.0))
+    assert float((torch.tensor(1.0) / (torch.tensor(2.0) + torch.tensor(2.0) - torch.tensor(1.0)))) == third
+    assert nms_keep(pair.cuda(), zeros(2).cuda(), third).cpu().tolist() == rcnn_ref.nms_sorted(pair, zeros(2), third).tolist() == [True, True]
+    below = float(torch.nextafter(torch.tensor(third), torch.tensor(0.0)))                  # IoU == thr is kept, one ulp below is not
+    assert nms_keep(pair.cuda(), zeros(2).cuda(), below).cpu().tolist() == rcnn_ref.nms_sorted(pair, zeros(2), below).tolist() == [True, False]
+    n = 4097                                                                                 # 65 matrix words: more words than lanes in the fold loop
+    xy = torch.rand((n, 2), generator=g) * 300
+    boxes = torch.cat([xy, xy + torch.rand((n, 2), generator=g) * 60 + 1], 1)
+    cats = torch.randint(0, 2, (n,), generator=g)
+    ref = rcnn_ref.nms_sorted(boxes, cats, 0.5)
+    assert torch.equal(ref, nms_keep(boxes.cuda(), cats.cuda(), 0.5).cpu()) and 0 < int(ref.sum()) < n
 
 
 def test_roi_align_matches_restatement():
@@ -140,6 +156,19 @@ def test_roi_align_matches_restatement():
         err = (got.permute(0, 3, 1, 2).cpu() - ref).abs().max().item()
         # the large boxes average up to ~20x20 bilinear samples per bin, in a different order than the oracle's loop
         assert err <= 5e-5, f"P={P}: {err:.3e}"
+    # rois without a single valid sample: entirely outside the map (every sample refused), and x1 < x0 (negative bin size:
+    # ceil <= 0 -> no samples, the count clamped to 1) -> zeros.  Against the loop oracle with the level given by hand
+    # (assign_levels takes the square root of a negative area).
+    odd = torch.tensor([[0.0, 1000.0, 1000.0, 1100.0, 1050.0], [1.0, -900.0, -800.0, -700.0, -650.0], [1.0, 2000.0, 10.0, 2400.0, 300.0],
+                        [0.0, 100.0, 50.0, 60.0, 120.0], [1.0, 200.0, 150.0, 40.0, 20.0], [0.0, 10.0, 10.0, 50.0, 40.0]])
+    odd_lv = torch.tensor([0, 1, 3, 0, 2, 0])
+    names = ("p2", "p3", "p4", "p5")
+    for P in (7, 14):
+        ref = torch.cat([rcnn_ref.roi_align(pyr[names[l]], odd[i:i + 1], 1.0 / (4 * 2 ** l), P, 0, True) for i, l in enumerate(odd_lv.tolist())])
+        got = roi_align_pyramid([_nhwc(pyr[k]) for k in names], odd.cuda(), odd_lv.cuda(), P).permute(0, 3, 1, 2).cpu()
+        assert float(ref[:5].abs().max()) == 0.0 and float(ref[5].abs().max()) > 0.0       # the last one is an ordinary roi
+        assert float(got[:5].abs().max()) == 0.0
+        assert (got - ref).abs().max().item() <= 5e-5
 
 
 def test_paste_masks_matches_restatement():
@@ -157,6 +186,20 @@ def test_paste_masks_matches_restatement():
     diff = ref != got
     assert ((vals - 0.5).abs()[diff] < 1e-6).all(), "mask differs away from the threshold"
     assert diff.float().mean().item() < 1e-4
+    # a box wholly outside the image, a box narrower than one pixel, and a constant 0.75 mask (the raster of its box)
+    boxes2 = torch.tensor([[-50.0, -40.0, -10.0, -5.0], [20.2, 10.0, 20.7, 40.0], [10.3, 5.6, 50.2, 33.9], [90.0, 70.0, 120.0, 95.0]])
+    probs2 = torch.rand((4, M, M), generator=g)
+    probs2[2] = 0.75
+    vals = rcnn_ref.paste_values(probs2, boxes2, (H, W))
+    ref = vals >= 0.5
+    got = paste_masks(probs2.cuda(), boxes2.cuda(), (H, W), 0.5).cpu()
+    diff = ref != got
+    assert ((vals - 0.5).abs()[diff] < 1e-6).all(), "mask differs away from the threshold"
+    assert diff.float().mean().item() < 1e-4
+    assert not ref[0].any() and not got[0].any() and not got[3].any() and ref[1].any()
+    inside = torch.zeros((H, W), dtype=torch.bool)
+    inside[7:33, 12:49] = True               # pixels whose centre lies at least one pixel inside the box: the constant mask covers them
+    assert bool(got[2][inside].all()) and bool(ref[2][inside].all())
     assert paste_masks(probs[:0].cuda(), boxes[:0].cuda(), (H, W), 0.5).shape == (0, H, W)
 
 
@@ -600,34 +643,14 @@ def test_r101_batch16_full_proposals_against_the_vectorised_oracle():
     net = MaskRCNN(cfg, sd)
     got = net.inference(img.cuda())
     assert len(got) == len(ref) == 16
+    from rcnn_cases import match_detections      # the matcher, shared with tests/test_rcnn_selection_gpu.py
     n_total, n_moved, worst_box, worst_score, worst_iou = 0, 0, 0.0, 0.0, 1.0
     for gi, ri in zip(got, ref):
         assert len(ri["proposals"]) == 1000
-        n = len(ri["scores"])
-        assert len(gi["scores"]) == n > 0
-        gs, gb, gc = gi["scores"].cpu(), gi["pred_boxes"].cpu(), gi["pred_classes"].cpu()
-        rs, rb, rc = ri["scores"], ri["pred_boxes"], ri["pred_classes"]
-        ok = (gc[None, :] == rc[:, None]) & ((gs[None, :] - rs[:, None]).abs() <= 1e-4) & \
-             ((gb[None, :, :] - rb[:, None, :]).abs().amax(2) <= 5e-2)                      # [ref i, got j]
-        perm = torch.full((n,), -1, dtype=torch.int64)
-        taken = torch.zeros(n, dtype=torch.bool)
-        for i in range(n):
-            cand = torch.nonzero(ok[i] & ~taken).flatten()
-            assert len(cand) > 0, f"oracle detection {i} (class {int(rc[i])}, score {float(rs[i]):.6f}) has no counterpart"
-            j = int(cand[(cand - i).abs().argmin()])
-            perm[i] = j
-            taken[j] = True
-        moved = torch.nonzero(perm != torch.arange(n)).flatten()
-        for i in moved.tolist():     # a rank can only differ inside a run of near-equal scores
-            lo, hi = min(i, int(perm[i])), max(i, int(perm[i]))
-            assert float(rs[lo] - rs[hi]) <= 2e-4
-        n_moved += len(moved)
-        worst_score = max(worst_score, (gs[perm] - rs).abs().max().item())
-        worst_box = max(worst_box, (gb[perm] - rb).abs().max().item())
-        gm, rm = gi["pred_masks"].cpu()[perm], ri["pred_masks"]
-        inter, union = (gm & rm).sum().item(), (gm | rm).sum().item()
-        worst_iou = min(worst_iou, inter / max(union, 1))
-        n_total += n
+        _, moved, ws, wb, iou = match_detections(gi, ri)
+        n_moved += moved
+        worst_score, worst_box, worst_iou = max(worst_score, ws), max(worst_box, wb), min(worst_iou, iou)
+        n_total += len(ri["scores"])
     print(f"R-101 B=16: {n_total} detections ({n_moved} at another rank inside a score tie), max |score diff| {worst_score:.2e}, "
           f"max |box diff| {worst_box:.2e} px, min mask IoU {worst_iou:.4f}")
     assert worst_score <= 1e-4 and worst_box <= 5e-2 and worst_iou >= 0.98 and n_moved <= n_total // 20
