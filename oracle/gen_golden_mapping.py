@@ -1,7 +1,8 @@
 """ORACLE support (test infrastructure): golden vectors for the map-projection path, produced by
 the reference's own ``Semantic_Mapping`` (imported unmodified from /root/reference/nav) on seeded
 synthetic sequences; also asserts that oracle/mapping_ref.py is bit-identical to it.
-Run via ``python -m oracle.gen_golden`` (build container only)."""
+Run via ``python -m oracle.gen_golden`` (build container only); ``python -m oracle.gen_golden_mapping --edges`` writes only
+``mapping_golden_edges.npz`` (oracle.mapping_scenes.edge_scenes) and leaves every other golden file as it is."""
 from __future__ import annotations
 
 import os
@@ -52,6 +53,7 @@ def generate(report):
             part[f"{name}/cfg_{k}"] = np.array(v)
         out.update(part)
     np.savez_compressed(os.path.join(GOLDEN, "mapping_golden_flags.npz"), **out)
+    generate_edges(report)
 
 
 def _generate(report, cfg, seqs, fname):
@@ -105,3 +107,75 @@ def _generate(report, cfg, seqs, fname):
     if fname:
         np.savez_compressed(os.path.join(GOLDEN, fname), **out)
     return out
+
+
+def _stairs_taken(obs, cfg):
+    coords = mapping_ref.point_cloud_std(obs[:, 3], cfg)
+    feat = torch.ones(1, 1 + cfg.num_sem_categories, obs.shape[2] * obs.shape[3])
+    feat[:, 1:] = obs[:, 4:].reshape(1, cfg.num_sem_categories, -1)
+    return bool(mapping_ref.stairs_mask(coords, feat).any())
+
+
+def generate_edges(report=None):
+    """The edge scenes (stairs rule at its thresholds, dense cells, grid limits, heading wrap, border starts) through the
+    reference's unmodified Semantic_Mapping, every scene from an empty map and its own start pose; the restatement must be
+    bit-identical on every frame.  Stored per scene: what the other mapping goldens store, plus the start pose.  A scene with
+    a ``source`` reuses that scene's depth / sem images and stores only its pose_obs."""
+    cfg = mapping_ref.MapCfg()
+    sm = reference_module(cfg)
+    torch.set_grad_enabled(False)
+    out = {}
+    M, C = cfg.map_cells, 4 + cfg.num_sem_categories
+    for sc in mapping_scenes.edge_scenes():
+        name, frames = sc["name"], sc["frames"]
+        maps_ref, maps_mine = torch.zeros(C, M, M), torch.zeros(C, M, M)
+        pose_ref = torch.tensor(sc["start"], dtype=torch.float32)
+        pose_mine = pose_ref.clone()
+        sums, nnz, poses, fps, stairs = [], [], [], [], []
+        for i, fr in enumerate(frames):
+            obs = torch.from_numpy(mapping_scenes.frame_to_obs(fr))[None]
+            rel = torch.from_numpy(fr["pose"])
+            fp_r, maps_ref, _, pose_ref = sm(obs, rel, maps_ref, pose_ref, None)
+            fp_m, maps_mine, _, pose_mine = mapping_ref.forward(obs, rel, maps_mine, pose_mine, cfg)
+            assert torch.equal(fp_r, fp_m), f"{name} frame {i}: fp_map_pred of the restatement deviates from the reference"
+            assert torch.equal(maps_ref, maps_mine), f"{name} frame {i}: map of the restatement deviates from the reference"
+            assert torch.equal(pose_ref, pose_mine), f"{name} frame {i}: pose of the restatement deviates from the reference"
+            sums.append(maps_ref.double().sum((1, 2)).numpy())
+            nnz.append((maps_ref != 0).sum((1, 2)).numpy())
+            poses.append(pose_ref.numpy().copy())
+            fps.append(np.packbits(fp_r.numpy().astype(bool)))
+            stairs.append(_stairs_taken(obs, cfg))
+        final = maps_ref.numpy()
+        idx = np.flatnonzero(final)
+        if sc["source"] is None:
+            depth = np.stack([f["depth"] for f in frames])
+            out[f"{name}/depth"] = depth
+            out[f"{name}/sem"] = np.stack([f["sem"] for f in frames])
+            out[f"{name}/depth_quantised"] = np.array(bool(np.array_equal(np.round(depth * 4.0) / 4.0, depth)))
+        else:
+            out[f"{name}/source"] = np.array(sc["source"])
+        out[f"{name}/start"] = np.asarray(sc["start"], np.float32)
+        out[f"{name}/pose_obs"] = np.stack([f["pose"] for f in frames])
+        out[f"{name}/channel_sums"] = np.stack(sums)
+        out[f"{name}/channel_nnz"] = np.stack(nnz)
+        out[f"{name}/poses"] = np.stack(poses)
+        out[f"{name}/fp_map_bits"] = np.stack(fps)
+        out[f"{name}/final_idx"] = idx.astype(np.int32)
+        out[f"{name}/final_val"] = final.reshape(-1)[idx].astype(np.float32)
+        out[f"{name}/stairs_branch"] = np.array(stairs)
+        if report is not None:
+            report.setdefault("mapping", {})[name] = dict(frames=len(frames), final_nnz=int(idx.size),
+                                                          stairs_frames=[i for i, s in enumerate(stairs) if s])
+        print(f"[mapping edges] {name}: {len(frames)} frames, restatement bit-identical, final nnz {idx.size}, "
+              f"stairs {[int(s) for s in stairs]}, fp cells {[int(np.unpackbits(f).sum()) for f in fps]}")
+    path = os.path.join(GOLDEN, "mapping_golden_edges.npz")
+    np.savez_compressed(path, **out)
+    print(f"[mapping edges] wrote {path}: {os.path.getsize(path)} bytes")
+    return out
+
+
+if __name__ == "__main__":
+    import sys
+    if "--edges" not in sys.argv:
+        raise SystemExit("usage: python -m oracle.gen_golden_mapping --edges   (everything else: python -m oracle.gen_golden)")
+    generate_edges()
