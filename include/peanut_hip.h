@@ -196,7 +196,9 @@ int peanut_pred_debug_read(peanut_pred_t* h, const char* name, float* dst_dev, s
  * HIP event before/after each launch ON THE STREAM THE KERNELS RUN ON.  collect() synchronises
  * on those events, sums each op's elapsed time over all forwards since the last collect and
  * clears the probe.  names/kernels point to storage owned by the handle (valid until the plan
- * is dropped); kernels[i] is the kernel family op i launches (e.g. "conv_pw_glds_128x128");
+ * is dropped); kernels[i] is the kernel family op i launches (e.g. "conv_pw_glds_128x128"): the
+ * plan takes it from the same route the launch takes, and a forward under the probe fails with
+ * PEANUT_EINVAL (both names in the message) if a conv op's launch recorded another family;
  * flops[i] = FLOPs one launch of op i executes; bytes[i] = its algorithmic HBM bytes (every operand read
  * once, the result written once).  Returns the op count. */
 int peanut_pred_probe_enable(peanut_pred_t* h, int enable);
@@ -353,7 +355,8 @@ int peanut_rcnn_forward_front(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, i
 
 /* Event probe of the front end (bench.py: stage-1 roofline): runs it `reps` times on `stream` with a HIP event after every
  * op, synchronises, and reports per op its name, the kernel family the launch picked (peanut_last_conv_kernel; "wino+..."
- * = Winograd transforms + that GEMM), the mean milliseconds and the direct-form conv FLOPs (0 for non-conv ops).  names /
+ * = Winograd transforms + that GEMM), the mean milliseconds and the direct-form conv FLOPs (0 for non-conv ops).  Fails with
+ * PEANUT_EINVAL if a conv op ran another family than its plan names (the route of csrc/conv_route.hip, asked twice).  names /
  * kernels point to storage owned by the handle (valid until the next probe or plan change).  Returns the op count. */
 int peanut_rcnn_probe_front(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int H, int W, int reps, int max_ops,
                             const char** names, const char** kernels, double* ms, double* flops, void* stream);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "persistent_plan.h"
+
 namespace peanut {
 
 // ---- error plumbing (thread-local message, negative codes; include/peanut_hip.h) ----
@@ -131,6 +133,41 @@ size_t conv_packed_floats(int cin_pad, int cout, int kh, int kw, int bn_tile);
 void pack_conv_weights(const float* w_oihw, int cout, int cin_real, int cin_pad, int kh, int kw,
                        int bn_tile, int bk, float* out);
 int launch_conv(const ConvDesc& d, const ConvArgs& a, hipStream_t stream);
+
+// ---- the conv route (conv_route.hip): which kernel runs a layer, decided ONCE for the launcher and the planners' op tables ----
+enum ConvKernelId {
+  CONV_K_INVALID,           // no kernel takes the launch: ConvRoute::code / error
+  CONV_K_GEMM_RS,           // gemm_rs.hip: pointwise layer / grouped GEMM of an emulated mode (tile bm x bn)
+  CONV_K_CONV_RS,           // conv_rs.hip: every other conv of an emulated mode (128 x bn)
+  CONV_K_GEMM_SKINNY,       // gemm_skinny.hip
+  CONV_K_PW_256X256P,       // conv_pw256wp.hip: persistent 256 x 256
+  CONV_K_PW_ARES,           // conv_pw_ares.hip
+  CONV_K_PW_256X256,        // conv_pw.hip: tile-per-workgroup 256 x 256
+  CONV_K_PW_256X128P,       // conv_pw256p.hip: persistent 256 x 128
+  CONV_K_PW_256X128,        // conv_pw.hip: tile-per-workgroup 256 x 128
+  CONV_K_PW_TILE,           // conv_pw.hip: 128 x bn (pack_bn = 128: 64-wide tiles over 128-wide packing)
+  CONV_K_PATCH,             // conv_patch.hip (bk = input channels, bn = output channels, stride)
+  CONV_K_PATCH_NCHW,        // ... its NCHW variant (launch_conv_patch_nchw)
+  CONV_K_IGEMM,             // conv_igemm.hip: 128 x bn x bk
+};
+struct ConvRoute {
+  ConvKernelId id;
+  int bm, bn, bk;           // the kernel variant's tile
+  int planes;               // emulation kind (ConvDesc::s_planes)
+  int stride;               // patch kernels
+  int pack_bn;              // ConvKParams::pack_bn
+  int G;                    // persistent kernels: workgroups (one per CU, a multiple of 8)
+  PersistentPlan plan;      // persistent kernels: the tail plan (persistent_plan.h)
+  int code;                 // CONV_K_INVALID: the error launch_conv fails with
+  const char* error;
+};
+struct ConvKParams;
+// Pure host function of the shapes, c1 / c2, res / ws != null, the weight groups, ws_floats and the options (opt()): never dereferences
+// a device pointer.  `params` (optional) receives the launch parameters the choice worked out (all but the zero page).
+ConvRoute conv_route(const ConvDesc& d, const ConvArgs& a, ConvKParams* params = nullptr);
+ConvRoute conv_route_patch_nchw();                       // the route of launch_conv_patch_nchw
+const char* conv_kernel_family(const ConvRoute& r);      // THE table of family names
+int device_cus();                                        // CUs of the current device (cached per device; 0: none)
 // true unless PEANUT_PW_GLDS=0: fp32 1x1 convs / grouped GEMMs run on the LDS-DMA kernel of conv_pw.hip
 bool conv_pw_enabled();
 // conv_pw.hip: whether a pointwise layer / grouped GEMM runs on the 256 x 128 three-stage kernel
@@ -143,9 +180,7 @@ bool conv_pw_narrow_tiles(int cin, int cout, long long M, int bn_tile, int mt_pe
 // conv_pw256p.hip: ... on the persistent 256 x 128 kernel (epilogue of the previous tile inside the next tile's k-loop)
 bool conv_pw_uses_256p(int cout, long long M, int mt_per_group, int bn_tile, int cin, int flush_ktiles, long long in_pixels = 0);
 // gemm_skinny.hip (round 6): a grouped pointwise launch with a handful of data rows per group (the PSP pyramid's per-scale convs at batch 1)
-struct ConvKParams;
 bool gemm_skinny_takes(const ConvKParams& p, int bn_tile, size_t ws_floats);
-int launch_gemm_skinny(const ConvKParams& p, float* ws, size_t ws_floats, hipStream_t stream);
 // conv_pw256wp.hip: ... on the persistent 256 x 256 kernel (in-place epilogue inside the next tile's first iteration); stride 1
 // only, c1 / c2 the channels of the two sources
 bool conv_pw_uses_256wp(int cout, long long M, int stride, int mt_per_group, int bn_tile, int c1, int c2, int flush_ktiles);
@@ -154,7 +189,6 @@ bool conv_pw_uses_ares(int cin, int cout, long long M, int stride, bool two_sour
 
 // conv_patch.hip: 3x3 convs with 16 / 32 input channels (the deep stem) on the persistent LDS-patch kernel
 bool conv_patch_eligible(const ConvDesc& d, const ConvArgs& a);
-const char* conv_patch_kernel_name(const ConvDesc& d, bool nchw);
 // ... and its NCHW variant: the network's first conv (16 padded channels, stride 2) straight from the caller's [B][creal][H][W] input
 bool conv_patch_nchw_eligible(const ConvDesc& d, int B, int Ho, int Wo, int creal);
 int launch_conv_patch_nchw(const ConvDesc& d, const float* x_nchw, int creal, float* y, int B, int H, int W, int Ho, int Wo, hipStream_t stream);
@@ -181,7 +215,8 @@ int launch_wino_output(const float* Mb, const float* scale, const float* shift, 
 // ---- emulated-fp32 GEMM on the bf16 matrix cores, fp32 activations split in registers (gemm_rs.hip) ----
 // whether the 256 x 256 kernel runs a [M x cout] output (mt_per_group: 128-row tiles per Winograd position, 0 = plain)
 bool gemm_rs_uses_256(int cout, long long M, int mt_per_group, int bn_tile, int cin);
-const char* gemm_rs_kernel_name(int cout, long long M, int mt_per_group, int bn_tile, int cin, int planes);
+// ... the 64 x 64 one (batch-1 shapes with short k-loops)
+bool gemm_rs_uses_64(int cout, long long M, int bn_tile, int cin);
 // the weights' pieces (planes = emulation kind), packed per (n-tile of bn_tile rows, k-tile of 16 channels, plane)
 size_t sx_packed_bytes(int cin_pad, int cout, int bn_tile, int planes);
 void pack_weights_sx(const float* w, int cout, int cin_real, int cin_pad, int bn_tile, int planes, float wscale, void* out);

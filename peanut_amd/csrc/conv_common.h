@@ -77,22 +77,26 @@ struct KIter {
 
 
 const float* zero_page();   // per-device 4 KiB of zeros (allocated on first use)
-// conv_pw.hip: fp32 pointwise convs / grouped GEMMs with LDS-DMA staging (PEANUT_PW_GLDS=0 disables)
-bool conv_pw_enabled();
-int launch_conv_pw(const ConvKParams& p, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream);
+// The launchers launch_conv switches into (common.h: ConvRoute): each runs the kernel the route named, none re-checks a gate.
+// conv_pw.hip: the tile-per-workgroup fp32 pointwise kernels with LDS-DMA staging (256 x 256, 256 x 128, 128 x bn)
+int launch_conv_pw(const ConvKParams& p, const ConvRoute& r, float* ws, size_t ws_floats, hipStream_t stream);
+// gemm_skinny.hip
+int launch_gemm_skinny(const ConvKParams& p, float* ws, size_t ws_floats, hipStream_t stream);
 // conv_pw_ares.hip: persistent A-resident kernel for the K = 128 / 256 pointwise layers and grouped GEMMs
 int launch_conv_pw_ares(const ConvKParams& p, int bn_tile, hipStream_t stream);
-// conv_pw256p.hip: persistent 256 x 128 kernel (p.ntiles = 128-wide n-tiles)
-int launch_conv_pw256p(const ConvKParams& p, float* ws, size_t ws_floats, hipStream_t stream);
-// conv_pw256wp.hip: persistent 256 x 256 kernel (returns 1 without launching when the tail's partial tiles do not fit the scratch)
-int launch_conv_pw256wp(const ConvKParams& p, float* ws, size_t ws_floats, hipStream_t stream);
+// conv_pw256p.hip: persistent 256 x 128 kernel (p.ntiles = 128-wide n-tiles); fails when the route's uniform split does not fit the scratch
+int launch_conv_pw256p(const ConvKParams& p, const ConvRoute& r, float* ws, hipStream_t stream);
+// conv_pw256wp.hip: persistent 256 x 256 kernel
+int launch_conv_pw256wp(const ConvKParams& p, const ConvRoute& r, float* ws, hipStream_t stream);
 // conv_patch.hip: persistent LDS-patch kernel for the 3x3 convs with 16 / 32 input channels (gate: conv_patch_eligible)
 int launch_conv_patch(const ConvKParams& p, const ConvDesc& d, int B, hipStream_t stream);
 // gemm_rs.hip: pointwise layer / grouped GEMM emulated on the bf16 matrix cores: fp32 A (p.x, p.x2) split into bf16 pieces in
-// registers, p.w = the weights' pre-split pieces, nkt = cin / 16
-int launch_gemm_rs(const ConvKParams& p, int bn_tile, int planes, float* ws, size_t ws_floats, hipStream_t stream);
+// registers, p.w = the weights' pre-split pieces, nkt = cin / 16; the route's tile (64 x 64, 256 x 256, 128 x 128 / 64)
+int launch_gemm_rs(const ConvKParams& p, const ConvRoute& r, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream);
 // conv_rs.hip: every other conv in the emulated-fp32 modes (implicit GEMM, p.w = pack_weights_sx_conv weights, nkt = cin / 16 * taps)
 int launch_conv_rs(const ConvKParams& p, int bn_tile, int planes, float* ws, size_t ws_floats, hipStream_t stream);
+// conv_igemm.hip: the implicit-GEMM kernel, 128 x bn x bk
+int launch_conv_igemm(const ConvKParams& p, int bn_tile, int bk, float* ws, size_t ws_floats, hipStream_t stream);
 
 
 // Work decomposition of one launch.
@@ -419,7 +423,8 @@ int launch_with_tail_split(KernelT kernel, ConvKParams p, float* ws, size_t ws_f
   int slots = cache->slots[dev].load(std::memory_order_relaxed), cus = cache->cus[dev].load(std::memory_order_relaxed);
   if (slots == 0) {
     int occ = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+    cus = device_cus();
+    if (cus < 1 ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, NT, 0) != hipSuccess || occ < 1)
       slots = -1;
     else

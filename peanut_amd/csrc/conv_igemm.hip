@@ -287,7 +287,7 @@ void conv_pick_tiles(int cin_pad, int cout, int* bn_tile, int* bk, bool pointwis
   // overlap better.  Measured (profiles/r2h): layer1 conv3 0.37 -> 0.30 ms, layer2 conv3 0.24 -> 0.20, layer3 conv3
   // 0.645 -> 0.573; larger K loses (the matrix-core share grows).  Option bn64_maxk overrides the threshold.
   // Pointwise layers (round 4): only up to pw_bn64_maxk (128) channels are PACKED 64 wide; a 129..256-channel layer is packed 128
-  // wide and launch_conv_pw picks the 64-wide tile per shape (conv_pw_glds_kernel<64> reads halves of the 128-row packed tiles).
+  // wide and the route picks the 64-wide tile per shape (conv_pw_narrow_tiles) (conv_pw_glds_kernel<64> reads halves of the 128-row packed tiles).
   const int bn64_maxk = (int)opt(pointwise ? OPT_PW_BN64_MAXK : OPT_BN64_MAXK);
   if (*bn_tile == 128 && cin_pad <= bn64_maxk) *bn_tile = 64;
 }
@@ -324,61 +324,15 @@ static int launch_t(const ConvKParams& p, float* ws, size_t ws_floats, hipStream
       &conv_igemm_kernel<BM, BN, BK, WM, WN>, p, ws, ws_floats, stream, &slots);
 }
 
-int launch_conv(const ConvDesc& d, const ConvArgs& a, hipStream_t stream) {
-  if (a.c1 + a.c2 != d.cin) return fail(-2, "launch_conv: c1 + c2 != cin");
-  // gemm_rs.hip reads two sources at one pixel stride only for stride 1; a strided two-source pointwise layer of an emulated
-  // mode runs on the fp32 MFMA kernels instead (its fp32-packed weights are always uploaded; exact fp32: nothing is lost)
-  const bool rs_fallback = d.rs == 1 && a.c2 != 0 && d.stride != 1;
-  const int kgran = (d.rs && !rs_fallback) ? 16 : d.bk;     // k-tile of the kernel that will run
-  if (a.c1 % kgran != 0 || (a.c2 % kgran) != 0) return fail(-2, "launch_conv: channel split not a multiple of the k-tile");
-  ConvKParams p{};
-  p.x = a.x; p.x2 = a.x2 ? a.x2 : a.x; p.w = d.w_packed; p.scale = d.scale; p.shift = d.shift;
-  p.res = a.res; p.y = a.y;
-  p.zeros = zero_page();
-  if (!p.zeros) return fail(-3, "launch_conv: zero page allocation failed");
-  p.H = a.H; p.W = a.W; p.c1 = a.c1; p.c2 = a.c2; p.Ho = a.Ho; p.Wo = a.Wo; p.cout = d.cout;
-  p.kw = d.kw; p.ntaps = d.kh * d.kw; p.stride = d.stride; p.pad = d.pad; p.dil = d.dil; p.relu = d.relu;
-  p.HoWo = a.Ho * a.Wo;
-  const long long M = (long long)a.B * p.HoWo;
-  if (M <= 0 || M > 0x7fffffffLL || (long long)a.B * a.H * a.W > 0x7fffffffLL)
-    return fail(-2, "launch_conv: problem size out of range");
-  p.M = (int)M;
-  p.nkt = (d.cin / d.bk) * p.ntaps;
-  p.ntiles = d.cout_pad / d.bn_tile;
-  p.n_full = 0; p.n_sp = 0; p.split_p = 1; p.partial = nullptr;
-  p.alpha = 1.f;
-  p.flush = (d.rs && !rs_fallback) ? 0 : d.flush_ch / d.bk;   // k-tiles per partial sum (conv_pw.hip; every other kernel keeps one running sum)
-  p.mt_per_group = a.mt_per_group; p.w_group_stride = (long long)a.w_group_stride; p.ss_group_stride = a.ss_group_stride;
-  p.group_valid = a.mt_per_group ? a.group_valid_rows : 0;
-  if (a.defer) a.defer->valid = false;      // set by launch_with_tail_split alone, when it left its partial tiles unsummed
-  p.defer = a.defer;
-  p.group_rows = a.mt_per_group ? a.group_rows : nullptr;
-  if (d.rs && !rs_fallback) {   // emulated-fp32 GEMM on the bf16 matrix cores, fp32 activations split in registers
-    if (!d.w_s) return fail(-2, "launch_conv: register-split layer without pre-split weights");
-    p.w = static_cast<const float*>(d.w_s);
-    p.nkt = (d.cin / 16) * p.ntaps;
-    p.alpha = d.s_alpha;
-    if (d.rs == 2) return launch_conv_rs(p, d.bn_tile, d.s_planes, a.ws, a.ws_floats, stream);
-    return launch_gemm_rs(p, d.bn_tile, d.s_planes, a.ws, a.ws_floats, stream);
+int launch_conv_igemm(const ConvKParams& p, int bn_tile, int bk, float* ws, size_t ws_floats, hipStream_t stream) {
+  if (bk == 32) {
+    if (bn_tile == 128) return launch_t<128, 128, 32, 2, 2>(p, ws, ws_floats, stream);
+    if (bn_tile == 64) return launch_t<128, 64, 32, 2, 2>(p, ws, ws_floats, stream);
+    return launch_t<128, 32, 32, 4, 1>(p, ws, ws_floats, stream);
   }
-  if (d.bk == 32 && p.ntaps == 1 && p.pad == 0 && p.c1 % 32 == 0 && p.c2 % 32 == 0 && (p.c2 == 0 || p.stride == 1) && conv_pw_enabled())
-    return launch_conv_pw(p, d.bn_tile, a.ws, a.ws_floats, stream);
-  if (conv_patch_eligible(d, a)) return launch_conv_patch(p, d, a.B, stream);
-  {
-    static const char* const names[2][3] = {{"conv_igemm_128x128x32", "conv_igemm_128x64x32", "conv_igemm_128x32x32"},
-                                            {"conv_igemm_128x128x16", "conv_igemm_128x64x16", "conv_igemm_128x32x16"}};
-    note_kernel(names[d.bk == 32 ? 0 : 1][d.bn_tile == 128 ? 0 : (d.bn_tile == 64 ? 1 : 2)]);
-  }
-  if (d.bk == 32) {
-    if (d.bn_tile == 128) return launch_t<128, 128, 32, 2, 2>(p, a.ws, a.ws_floats, stream);
-    if (d.bn_tile == 64) return launch_t<128, 64, 32, 2, 2>(p, a.ws, a.ws_floats, stream);
-    if (d.bn_tile == 32) return launch_t<128, 32, 32, 4, 1>(p, a.ws, a.ws_floats, stream);
-  } else if (d.bk == 16) {
-    if (d.bn_tile == 128) return launch_t<128, 128, 16, 2, 2>(p, a.ws, a.ws_floats, stream);
-    if (d.bn_tile == 64) return launch_t<128, 64, 16, 2, 2>(p, a.ws, a.ws_floats, stream);
-    if (d.bn_tile == 32) return launch_t<128, 32, 16, 4, 1>(p, a.ws, a.ws_floats, stream);
-  }
-  return fail(-2, "launch_conv: unsupported tile configuration");
+  if (bn_tile == 128) return launch_t<128, 128, 16, 2, 2>(p, ws, ws_floats, stream);
+  if (bn_tile == 64) return launch_t<128, 64, 16, 2, 2>(p, ws, ws_floats, stream);
+  return launch_t<128, 32, 16, 4, 1>(p, ws, ws_floats, stream);
 }
 
 }  // namespace peanut

@@ -293,12 +293,6 @@ int launch_patch_t(const ConvKParams& p, int B, int cus, int per_cu, int creal, 
   return e == hipSuccess ? 0 : fail(-3, std::string("conv_patch launch: ") + hipGetErrorString(e));
 }
 
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  return cus;
-}
-
 // Which layers take it: 3 x 3, pad 1, no dilation, ONE source of 16 or 32 (padded) channels packed with bk = cin (k-tile =
 // tap), 32 or 64 output channels in one n-tile, no residual, no weight groups; stride 1, or 2 with 16 channels (a stride-2
 // patch of 32 channels does not fit LDS); at least patch_mintiles output tiles of 8 x 16 pixels (below that a
@@ -323,13 +317,6 @@ bool conv_patch_eligible(const ConvDesc& d, const ConvArgs& a) {
   return tiles >= min_tiles && tiles < 0x7fffffffLL;
 }
 
-// family name launch_conv_patch / launch_conv_patch_nchw note for a layer the gates admit (the planner's op tables)
-const char* conv_patch_kernel_name(const ConvDesc& d, bool nchw) {
-  if (nchw) return "conv_patch_nchw_16x32s2";
-  if (d.cin == 32) return d.cout == 64 ? "conv_patch_32x64s1" : "conv_patch_32x32s1";
-  return d.stride == 1 ? "conv_patch_16x32s1" : "conv_patch_16x32s2";
-}
-
 // the network's first conv straight from the NCHW input (option stem_nchw): 16-channel stride-2 layer, <= 16 real channels
 bool conv_patch_nchw_eligible(const ConvDesc& d, int B, int Ho, int Wo, int creal) {
   const long long min_tiles = opt(OPT_PATCH_MINTILES);
@@ -342,7 +329,6 @@ bool conv_patch_nchw_eligible(const ConvDesc& d, int B, int Ho, int Wo, int crea
 int launch_conv_patch(const ConvKParams& p, const ConvDesc& d, int B, hipStream_t stream) {
   const int cus = device_cus();
   if (cus < 1) return fail(-3, "conv_patch: no current device");
-  note_kernel(conv_patch_kernel_name(d, false));
   if (d.cin == 32 && d.cout == 64) return launch_patch_t<32, 64, 1, 8, 2, 2, false>(p, B, cus, 1, 0, stream);
   if (d.cin == 32 && d.cout == 32) return launch_patch_t<32, 32, 1, 16, 1, 2, false>(p, B, cus, 1, 0, stream);
   if (d.cin == 16 && d.stride == 1) return launch_patch_t<16, 32, 1, 16, 1, 2, false>(p, B, cus, 1, 0, stream);
@@ -361,7 +347,7 @@ int launch_conv_patch_nchw(const ConvDesc& d, const float* x_nchw, int creal, fl
   p.H = H; p.W = W; p.c1 = d.cin; p.c2 = 0; p.Ho = Ho; p.Wo = Wo; p.cout = d.cout;
   p.kw = 3; p.ntaps = 9; p.stride = d.stride; p.pad = 1; p.dil = 1; p.relu = d.relu;
   p.HoWo = Ho * Wo; p.M = B * Ho * Wo; p.alpha = 1.f;
-  note_kernel(conv_patch_kernel_name(d, true));
+  note_kernel(conv_kernel_family(conv_route_patch_nchw()));
   return launch_patch_t<16, 32, 2, 8, 1, 1, true>(p, B, cus, 2, creal, stream);
 }
 

@@ -514,53 +514,31 @@ bool conv_pw_narrow_tiles(int cin, int cout, long long M, int bn_tile, int mt_pe
   return ((M + 127) / 128) * (cout / 128) < opt(OPT_PW64_MAXTILES);
 }
 
-// fp32, BK = 32, 1x1, pad 0, one source (checked by the caller)
-int launch_conv_pw(const ConvKParams& p, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream) {
-  const int phase_shift_w = opt(OPT_PW256_PHASE) != 0;
-  // a handful of data rows per weight group (the PSP pyramid at batch 1): weight streaming, no LDS (gemm_skinny.hip)
-  if (gemm_skinny_takes(p, bn_tile, ws ? ws_floats : 0)) return launch_gemm_skinny(p, ws, ws_floats, stream);
-  // (the persistent 256 x 256 kernel first: its gate starts at 512 input channels by default, above the A-resident kernel's K = 128 / 256
-  // layers; lowering pw256wp_mink hands those to it)
-  if (conv_pw_uses_256wp(p.cout, p.M, p.stride, p.mt_per_group, bn_tile, p.c1, p.c2, p.flush)) {
-    const int rc = launch_conv_pw256wp(p, ws, ws_floats, stream);
-    if (rc != 1) return rc;
-  }
-  if (conv_pw_uses_ares(p.c1, p.cout, p.M, p.stride, p.c2 != 0, p.flush, bn_tile)) return launch_conv_pw_ares(p, bn_tile, stream);
-  if (conv_pw_uses_256w(p.cout, p.M, p.mt_per_group, bn_tile, p.c1 + p.c2, p.flush)) {
+// the tile-per-workgroup kernels of this file, as the route chose (conv_route.hip)
+int launch_conv_pw(const ConvKParams& p, const ConvRoute& r, float* ws, size_t ws_floats, hipStream_t stream) {
+  ConvKParams q = p;
+  if (r.id == CONV_K_PW_256X256) {
     static SlotCache slots256w;
-    ConvKParams q = p;
     q.ntiles = p.cout / 256;
-    q.phase_shift = phase_shift_w;
-    note_kernel("conv_pw_glds_256x256");
+    q.phase_shift = opt(OPT_PW256_PHASE) != 0;
     return launch_with_tail_split<decltype(&conv_pw_glds256w_kernel), 256, 256, 512>(&conv_pw_glds256w_kernel, q, ws, ws_floats, stream,
                                                                                       &slots256w);
   }
-  if (conv_pw_uses_256p(p.cout, p.M, p.mt_per_group, bn_tile, p.c1 + p.c2, p.flush, (long long)(p.M / p.HoWo) * p.H * p.W) && !(p.flush && p.res)) {
-    const int rc = launch_conv_pw256p(p, ws, ws_floats, stream);
-    if (rc != 1) return rc;            // 1: more items per workgroup than its plan table holds -> the kernels below
-  }
-  if (conv_pw_uses_256(p.cout, p.M, p.mt_per_group, bn_tile, p.c1 + p.c2)) {
+  if (r.id == CONV_K_PW_256X128) {
     static SlotCache slots256;
-    ConvKParams q = p;
     if (q.mt_per_group) q.mt_per_group /= 2;       // 256-row tiles per weight group
-    q.phase_shift = phase_shift_w;
+    q.phase_shift = opt(OPT_PW256_PHASE) != 0;
     if (opt(OPT_PW256_SKIP_PAD) == 0) q.group_valid = 0;
-    note_kernel("conv_pw_glds_256x128");
     return launch_with_tail_split<decltype(&conv_pw_glds256_kernel), 256, 128, 512>(&conv_pw_glds256_kernel, q, ws, ws_floats, stream,
                                                                                      &slots256);
   }
-  if (conv_pw_narrow_tiles(p.c1 + p.c2, p.cout, p.M, bn_tile, p.mt_per_group)) {      // 64-wide tiles over 128-wide packing
-    ConvKParams q = p;
-    q.pack_bn = 128;
+  if (r.pack_bn) {      // 64-wide tiles over 128-wide packing
+    q.pack_bn = r.pack_bn;
     q.ntiles = p.ntiles * 2;
-    note_kernel("conv_pw_glds_128x64");
-    return launch_pw_t<64, 2, 2>(q, ws, ws_floats, stream);
   }
-  note_kernel(bn_tile == 128 ? "conv_pw_glds_128x128" : (bn_tile == 64 ? "conv_pw_glds_128x64" : "conv_pw_glds_128x32"));
-  if (bn_tile == 128) return launch_pw_t<128, 2, 2>(p, ws, ws_floats, stream);
-  if (bn_tile == 64) return launch_pw_t<64, 2, 2>(p, ws, ws_floats, stream);
-  if (bn_tile == 32) return launch_pw_t<32, 4, 1>(p, ws, ws_floats, stream);
-  return fail(-2, "launch_conv_pw: unsupported tile configuration");
+  if (r.bn == 128) return launch_pw_t<128, 2, 2>(q, ws, ws_floats, stream);
+  if (r.bn == 64) return launch_pw_t<64, 2, 2>(q, ws, ws_floats, stream);
+  return launch_pw_t<32, 4, 1>(q, ws, ws_floats, stream);
 }
 
 }  // namespace peanut

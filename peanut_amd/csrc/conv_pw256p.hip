@@ -65,8 +65,7 @@ __global__ __launch_bounds__(512) void conv_pw_glds256p_kernel(const ConvKParams
   constexpr int A_INSTR = 4, B_INSTR = 2;
   // ONE LDS object: the three stages and, behind them, the workgroup's plan table (a second __shared__ variable would make hipcc
   // attach alias scopes to the LDS accesses and wait `vmcnt(0)` between every LDS-DMA request and the fragment reads: conv_pw256wp.hip)
-  constexpr int kMaxItems = 120;
-  __shared__ __attribute__((aligned(1024))) float smem[3 * STAGE + kMaxItems * 8];
+  __shared__ __attribute__((aligned(1024))) float smem[3 * STAGE + kMaxItems * 8];      // kMaxItems: persistent_plan.h
   int* const plan = reinterpret_cast<int*>(smem + 3 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -474,71 +473,24 @@ bool conv_pw_uses_256p(int cout, long long M, int mt_per_group, int bn_tile, int
   return ((M + 255) / 256) * (cout / 128) >= opt(OPT_PW256P_MINTILES);
 }
 
-int launch_conv_pw256p(const ConvKParams& p0, float* ws, size_t ws_floats, hipStream_t stream) {
+// the route's tail plan (persistent_plan.h) rides in r: r.G workgroups, one per CU
+int launch_conv_pw256p(const ConvKParams& p0, const ConvRoute& r, float* ws, hipStream_t stream) {
   ConvKParams p = p0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    return fail(-3, "conv_pw256p: no current device");
+  const PersistentPlan& pl = r.plan;
+  if (!pl.scratch_ok) return fail(-2, "conv_pw256p: split-K scratch too small");
+  const int G = r.G;
   const int mtiles = (p.M + 255) / 256;
-  const int T = mtiles * p.ntiles;
-  const int G = cus - cus % 8;          // one workgroup per CU whatever the tile count: a launch with fewer tiles than CUs is all split parts
-  // Every workgroup gets the same number of whole tiles (n_full / G); the T mod G tiles left over are cut into split_p
-  // k-ranges each (raw partial tiles + the ordered reduce, as in launch_with_tail_split) and dealt out evenly.  split_p
-  // minimises the busiest workgroup's extra work: ceil(t * p / G) parts of nkt / p k-tiles plus ~1.5 k-tile times per part (raw
-  // store, cursor switch); parts keep at least four k-tiles, preferably eight (the previous epilogue rides on eight iterations).
-  const int t = T % G;
-  int sp = 1;
-  if (t > 0) {
-    double best = 1e30;
-    for (int cand = 1; cand <= 16 && p.nkt / cand >= 4; ++cand) {
-      if (ws == nullptr || (size_t)t * cand * 256 * 128 > ws_floats) break;
-      const double parts = (double)(((long long)t * cand + G - 1) / G);
-      const double cost = parts * ((double)p.nkt / cand + 1.5 + (p.nkt / cand < 8 ? 2.0 : 0.0));
-      if (cost < best - 1e-9) { best = cost; sp = cand; }
-    }
-  }
-  p.split_p = sp;
-  p.n_sp = t * sp;
-  p.n_full = T - t;
-  // Stream-K for the tail (round 4): its t * nkt k-tiles as one stream, cut into equal runs for the first sk_g workgroups (runs of
-  // at least four k-tiles).  Against the uniform split above -- whose parts come in whole multiples per workgroup (132 tail tiles
-  // cut three ways = 396 parts over 256 workgroups: two parts for most, 21 k-tiles where 16.5 would do) -- every workgroup ends
-  // within one k-tile of the others.  A tile then has up to sk_maxp fragments; the reduce sums them in workgroup order.
-  p.sk_units = 0; p.sk_maxp = 0; p.sk_g = 0; p.sk_q = 1;
-  // (only for tails of at least a quarter of a round: measured per layer, profiles/r6b -- 132 tail tiles of 32 k-tiles 0.502 -> 0.489 ms,
-  // 8 or 32 tail tiles level or 1 % slower: their runs are a few k-tiles long and all fragments)
-  // The two-level accumulation variant streams in units of TWO k-tiles (one partial sum of 64 channels): its register epilogue
-  // hands the previous item's totals out during the next item's first two iterations, so no fragment may be shorter, and partial
-  // sums then cover the same channel groups as in an uncut tile.
-  const int q = p.flush ? 2 : 1;
-  if (t * 4 >= G && opt(OPT_PW256P_STREAMK) != 0 && ws != nullptr && p.nkt % q == 0) {
-    const int upt = p.nkt / q;                                      // stream units per tile
-    const long long U = (long long)t * upt;
-    const int Gs = (int)std::min<long long>(G, std::max<long long>(1, U * q / 4));
-    const int run = (int)(U / Gs);                                  // shortest run, in units
-    const int maxp = run > 0 ? (upt + run - 1) / run + 1 : 0;
-    const double parts_now = (double)(((long long)t * sp + G - 1) / G);
-    const double cost_now = parts_now * ((double)p.nkt / sp + 1.5 + (p.nkt / sp < 8 ? 2.0 : 0.0));
-    const double cost_stream = (double)((U + Gs - 1) / Gs) * q + 3.0;  // a run is two fragments on average: two raw stores / cursor switches
-    if (run * q >= 4 && (size_t)t * maxp * 256 * 128 <= ws_floats && cost_stream < cost_now - 0.5) {
-      p.sk_units = (int)U; p.sk_maxp = maxp; p.sk_g = Gs; p.sk_q = q;
-      p.n_sp = 0; p.split_p = 1;
-    }
-  }
-  if (p.n_sp > 0 && (!ws || (size_t)p.n_sp * 256 * 128 > ws_floats)) return fail(-2, "conv_pw256p: split-K scratch too small");
-  // more items per workgroup than the LDS plan table holds (a layer near the 4 GiB output bound, or a part with few CUs): nothing is
-  // launched and the caller takes the tile-per-workgroup kernel, as launch_conv_pw256wp's callers do
-  if (p.n_full / G + (p.n_sp + G - 1) / G + 4 > 120) return 1;
+  const int t = mtiles * p.ntiles - pl.n_full;      // tail tiles
+  p.split_p = pl.split_p; p.n_sp = pl.n_sp; p.n_full = pl.n_full;
+  p.sk_units = pl.sk_units; p.sk_maxp = pl.sk_maxp; p.sk_g = pl.sk_g; p.sk_q = pl.sk_q;
   p.partial = ws;
   p.mtiles = mtiles;
   p.nchunk = (int)opt(OPT_NCHUNK);
   p.phase_shift = opt(OPT_PW256_PHASE) != 0;
   p.p_order = opt(OPT_PW256P_ORDER) != 0;
-  note_kernel("conv_pw_glds_256x128p");
   if (p.mt_per_group) p.mt_per_group /= 2;       // 256-row tiles per weight group
   const bool ragged = p.M % 256 != 0;
   if (p.flush) {
-    if (p.res) return fail(-2, "conv_pw256p: the two-level accumulation variant takes no residual");
     if (ragged) hipLaunchKernelGGL((conv_pw_glds256p_kernel<true, true>), dim3((unsigned)G), dim3(512), 0, stream, p);
     else hipLaunchKernelGGL((conv_pw_glds256p_kernel<false, true>), dim3((unsigned)G), dim3(512), 0, stream, p);
   } else {

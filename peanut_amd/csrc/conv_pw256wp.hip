@@ -39,8 +39,6 @@ constexpr int wait_vm(int n) {                        // vmcnt(n), n <= 63 (a la
 }
 constexpr int kWaitLgkm0 = 0xC07F;                    // lgkmcnt(0)
 
-constexpr int kMaxItems = 120;                       // items (whole tiles + tail fragments) of one workgroup: the plan table in LDS
-
 // lane value (< 2^24) x uniform (< 2^24): one v_mul_u32_u24
 __device__ __forceinline__ unsigned lane_mul24(unsigned a, unsigned b) { return __umul24(a, b); }
 
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(512) void conv_pw_glds256wp_kernel(const ConvKParam
   static_assert(NPRE == 4 || NPRE == 2, "blocks per epilogue group");
   // ONE LDS object (the plan table behind the two stages): with a second __shared__ variable hipcc attaches alias scopes to the
   // LDS accesses and then puts an `s_waitcnt vmcnt(0)` between every LDS-DMA request and the fragment reads that follow it
-  __shared__ __attribute__((aligned(1024))) float smem[2 * STAGE + kMaxItems * 8];
+  __shared__ __attribute__((aligned(1024))) float smem[2 * STAGE + kMaxItems * 8];      // kMaxItems: persistent_plan.h
   int* const plan = reinterpret_cast<int*>(smem + 2 * STAGE);
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -485,54 +483,19 @@ bool conv_pw_uses_256wp(int cout, long long M, int stride, int mt_per_group, int
   return (M / 256) * (cout / 256) >= opt(OPT_PW256WP_MINTILES);
 }
 
-// returns 1 (nothing launched) when the tail's partial tiles do not fit the scratch
-int launch_conv_pw256wp(const ConvKParams& p0, float* ws, size_t ws_floats, hipStream_t stream) {
+// the route's tail plan (persistent_plan.h) rides in r: r.G workgroups, one per CU; the scratch holds the tail's raw partial tiles,
+// then one dump tile (the target of every workgroup's first, empty epilogue)
+int launch_conv_pw256wp(const ConvKParams& p0, const ConvRoute& r, float* ws, hipStream_t stream) {
   ConvKParams p = p0;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    return fail(-3, "conv_pw256wp: no current device");
-  constexpr size_t kTile = (size_t)256 * 256;
+  const PersistentPlan& pl = r.plan;
+  constexpr size_t kTile = kPersistent256x256.tile_floats;
+  const int G = r.G;
   p.ntiles = p.cout / 256;
   const int mtiles = p.M / 256;
-  const int T = mtiles * p.ntiles;
-  const int G = cus - cus % 8;
-  // The plan of launch_conv_pw256p: every workgroup the same number of whole tiles; the T mod G tiles left over as a uniform
-  // split (small tails) or as one stream of k-tiles in equal runs (tails of at least a quarter of a round).
-  const int t = T % G;
-  int sp = 1;
-  if (t > 0) {
-    double best = 1e30;
-    for (int cand = 1; cand <= 16 && p.nkt / cand >= 2; ++cand) {
-      if (ws == nullptr || (size_t)t * cand * kTile > ws_floats) break;
-      const double parts = (double)(((long long)t * cand + G - 1) / G);
-      const double cost = parts * ((double)p.nkt / cand + 1.0);
-      if (cost < best - 1e-9) { best = cost; sp = cand; }
-    }
-  }
-  p.split_p = sp;
-  p.n_sp = t * sp;
-  p.n_full = T - t;
-  // stream-K tail in units of TWO k-tiles: every fragment then has at least the two iterations the kernel's item loop needs
-  p.sk_units = 0; p.sk_maxp = 0; p.sk_g = 0; p.sk_q = 2;
-  if (t * 4 >= G && opt(OPT_PW256P_STREAMK) != 0 && ws != nullptr && p.nkt % 2 == 0) {
-    const int upt = p.nkt / 2;
-    const long long U = (long long)t * upt;
-    const int Gs = (int)std::min<long long>(G, std::max<long long>(1, U / 2));
-    const int run = (int)(U / Gs);                                  // shortest run, in units
-    const int maxp = run > 0 ? (upt + run - 1) / run + 1 : 0;
-    const double parts_now = (double)(((long long)t * sp + G - 1) / G);
-    const double cost_now = parts_now * ((double)p.nkt / sp + 1.0);
-    const double cost_stream = (double)((U + Gs - 1) / Gs) * 2 + 2.0;
-    if (run >= 2 && (size_t)t * maxp * kTile <= ws_floats && cost_stream < cost_now - 0.5) {
-      p.sk_units = (int)U; p.sk_maxp = maxp; p.sk_g = Gs;
-      p.n_sp = 0; p.split_p = 1;
-    }
-  }
-  // scratch: the tail's raw partial tiles, then one dump tile (the target of every workgroup's first, empty epilogue)
-  const size_t part_tiles = p.sk_units > 0 ? (size_t)t * p.sk_maxp : (size_t)p.n_sp;
-  if (!ws || (part_tiles + 1) * kTile > ws_floats) return 1;                    // no scratch: the caller takes another kernel
-  p.dump = ws + part_tiles * kTile;
-  if (p.n_full / G + (p.n_sp + G - 1) / G + 4 > kMaxItems) return 1;            // the workgroup's plan table (whole tiles + its tail parts / <= 3 fragments)
+  const int t = mtiles * p.ntiles - pl.n_full;      // tail tiles
+  p.split_p = pl.split_p; p.n_sp = pl.n_sp; p.n_full = pl.n_full;
+  p.sk_units = pl.sk_units; p.sk_maxp = pl.sk_maxp; p.sk_g = pl.sk_g; p.sk_q = pl.sk_q;
+  p.dump = ws + pl.part_tiles * kTile;
   p.partial = ws;
   p.mtiles = mtiles;
   p.nchunk = (int)opt(OPT_NCHUNK);
@@ -540,7 +503,6 @@ int launch_conv_pw256wp(const ConvKParams& p0, float* ws, size_t ws_floats, hipS
   p.p_order = opt(OPT_PW256P_ORDER) != 0;
   p.mt_per_group = 0;
   p.stagger = (int)opt(OPT_PW256WP_STAGGER);
-  note_kernel("conv_pw_glds_256x256p");
   // blocks per epilogue group: with a residual two (32 residual registers; four would need 64 and the kernel then sits at the 256-register
   // limit with spills), without one four (fewer repeated fragment reads in an item's first iteration); pw256wp_npre = 2 forces two
   // the residual variant exists with two blocks per group only: <true, 4> compiled to 255 VGPRs + 4 spilled (20 B of scratch) and was

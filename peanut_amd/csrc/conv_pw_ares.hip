@@ -268,9 +268,8 @@ __global__ __launch_bounds__(512) void conv_pw_ares_kernel(const ConvKParams p) 
 
 template <int NK, bool FLUSH>
 int launch_ares_t(ConvKParams p, hipStream_t stream) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-    return fail(-3, "conv_pw_ares: no current device");
+  const int cus = device_cus();
+  if (cus < 8) return fail(-3, "conv_pw_ares: no current device");
   const long long U = (long long)p.mtiles * p.ntiles;
   long long G = U < cus ? U : cus;
   G -= G % 8;
@@ -302,7 +301,6 @@ int launch_conv_pw_ares(const ConvKParams& p0, int bn_tile, hipStream_t stream) 
   p.ares_pbn = bn_tile;
   p.mtiles = p.M / 128;
   p.ntiles = p.cout / 128;
-  note_kernel("conv_pw_ares_128x128");
   const bool flush = p.flush == 2;
   if (p.c1 == 256) return flush ? launch_ares_t<8, true>(p, stream) : launch_ares_t<8, false>(p, stream);
   return flush ? launch_ares_t<4, true>(p, stream) : launch_ares_t<4, false>(p, stream);

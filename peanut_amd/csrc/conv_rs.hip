@@ -219,10 +219,6 @@ void pack_weights_sx_conv(const float* w_oihw, int cout, int cin_real, int cin_p
 int launch_conv_rs(const ConvKParams& p, int bn_tile, int planes, float* ws, size_t ws_floats, hipStream_t stream) {
   if (p.c1 % 16 || p.c2 % 16 || planes < RS_BF16X3 || planes > RS_FP16X3 || (bn_tile != 128 && bn_tile != 64 && bn_tile != 32))
     return fail(-2, "launch_conv_rs: 16-channel granularity, a known emulation kind, 128 / 64 / 32-row weight tiles");
-  static const char* const names[3][3] = {{"conv_rs3_128x128", "conv_rs3_128x64", "conv_rs3_128x32"},
-                                          {"conv_rs6_128x128", "conv_rs6_128x64", "conv_rs6_128x32"},
-                                          {"conv_rs3h_128x128", "conv_rs3h_128x64", "conv_rs3h_128x32"}};
-  note_kernel(names[planes - 2][bn_tile == 128 ? 0 : (bn_tile == 64 ? 1 : 2)]);
   if (planes == RS_BF16X6) return launch_conv_rs_kind<RS_BF16X6>(p, bn_tile, ws, ws_floats, stream);
   if (planes == RS_FP16X3) return launch_conv_rs_kind<RS_FP16X3>(p, bn_tile, ws, ws_floats, stream);
   return launch_conv_rs_kind<RS_BF16X3>(p, bn_tile, ws, ws_floats, stream);

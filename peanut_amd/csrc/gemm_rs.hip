@@ -300,38 +300,26 @@ bool gemm_rs_uses_64(int cout, long long M, int bn_tile, int cin) {
   return cout % 64 == 0 && cin <= max_k && t128 < max_tiles;
 }
 
-// family names: gemm_rs6_* (bf16, six products), gemm_rs3_* (bf16, three), gemm_rs3h_* (fp16, three)
-const char* gemm_rs_kernel_name(int cout, long long M, int mt_per_group, int bn_tile, int cin, int planes) {
-  static const char* const names[3][4] = {{"gemm_rs3_64x64", "gemm_rs3_256x256", "gemm_rs3_128x128", "gemm_rs3_128x64"},
-                                          {"gemm_rs6_64x64", "gemm_rs6_256x256", "gemm_rs6_128x128", "gemm_rs6_128x64"},
-                                          {"gemm_rs3h_64x64", "gemm_rs3h_256x256", "gemm_rs3h_128x128", "gemm_rs3h_128x64"}};
-  const int k = planes - 2;
-  if (k < 0 || k > 2) return "gemm_rs?";
-  if (gemm_rs_uses_64(cout, M, bn_tile, cin)) return names[k][0];
-  if (gemm_rs_uses_256(cout, M, mt_per_group, bn_tile, cin)) return names[k][1];
-  return names[k][bn_tile == 128 ? 2 : 3];
-}
-
 namespace {
 template <int KIND>
-int launch_gemm_rs_kind(const ConvKParams& p, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream) {
-  if (gemm_rs_uses_64(p.cout, p.M, bn_tile, p.c1 + p.c2))
+int launch_gemm_rs_kind(const ConvKParams& p, const ConvRoute& r, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream) {
+  if (r.bm == 64)
     return bn_tile == 128 ? launch_rs_t<64, 64, 2, 2, KIND, 128>(p, ws, ws_floats, stream) : launch_rs_t<64, 64, 2, 2, KIND, 64>(p, ws, ws_floats, stream);
-  if (gemm_rs_uses_256(p.cout, p.M, p.mt_per_group, bn_tile, p.c1 + p.c2)) return launch_rs_t<256, 256, 4, 2, KIND, 128>(p, ws, ws_floats, stream);
+  if (r.bm == 256) return launch_rs_t<256, 256, 4, 2, KIND, 128>(p, ws, ws_floats, stream);
   if (bn_tile == 128) return launch_rs_t<128, 128, 2, 2, KIND, 128>(p, ws, ws_floats, stream);
   return launch_rs_t<128, 64, 2, 2, KIND, 64>(p, ws, ws_floats, stream);
 }
 }  // namespace
 
 // p.x / p.x2: fp32 A (two sources allowed), p.w: S-packed weights (bn_tile rows per packed tile), p.nkt = cin / 16
-int launch_gemm_rs(const ConvKParams& p, int bn_tile, int planes, float* ws, size_t ws_floats, hipStream_t stream) {
+int launch_gemm_rs(const ConvKParams& p, const ConvRoute& r, int bn_tile, float* ws, size_t ws_floats, hipStream_t stream) {
+  const int planes = r.planes;
   if (p.ntaps != 1 || p.pad != 0 || p.c1 % 16 || p.c2 % 16 || (p.c2 && p.stride != 1) || (bn_tile != 128 && bn_tile != 64) ||
       planes < RS_BF16X3 || planes > RS_FP16X3)
     return fail(-2, "launch_gemm_rs: needs a pointwise layer with 16-channel granularity and 64- or 128-row weight tiles");
-  note_kernel(gemm_rs_kernel_name(p.cout, p.M, p.mt_per_group, bn_tile, p.c1 + p.c2, planes));
-  if (planes == RS_BF16X6) return launch_gemm_rs_kind<RS_BF16X6>(p, bn_tile, ws, ws_floats, stream);
-  if (planes == RS_FP16X3) return launch_gemm_rs_kind<RS_FP16X3>(p, bn_tile, ws, ws_floats, stream);
-  return launch_gemm_rs_kind<RS_BF16X3>(p, bn_tile, ws, ws_floats, stream);
+  if (planes == RS_BF16X6) return launch_gemm_rs_kind<RS_BF16X6>(p, r, bn_tile, ws, ws_floats, stream);
+  if (planes == RS_FP16X3) return launch_gemm_rs_kind<RS_FP16X3>(p, r, bn_tile, ws, ws_floats, stream);
+  return launch_gemm_rs_kind<RS_BF16X3>(p, r, bn_tile, ws, ws_floats, stream);
 }
 
 }  // namespace peanut

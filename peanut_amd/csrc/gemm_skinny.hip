@@ -211,7 +211,6 @@ int launch_gemm_skinny(const ConvKParams& p, float* ws, size_t ws_floats, hipStr
       a.chunk_rows[nchunks] = (unsigned char)std::min(kSkinnyChunkRows, a.grp_rows[g] - m0);
       ++nchunks;
     }
-  note_kernel("gemm_skinny");
   hipLaunchKernelGGL(gemm_skinny_kernel, dim3((unsigned)(a.ntiles * ksplit), (unsigned)nchunks), dim3(256), 0, stream, a);
   SkinnyEpi e{};
   e.partial = ws; e.scale = p.scale; e.shift = p.shift; e.y = p.y;

@@ -396,29 +396,44 @@ inline bool conv_layer_accepts_deferred(const ConvLayer& L, int B, int H, int W)
   return wino_input_accepts_deferred(B, H, W, L.d.cin, L.d.dil, wino_gran_for(L, B, H, W), L.wino_m);
 }
 
+// Workspace base a planner builds an op's ConvArgs with: plans are made before the workspace exists, and the route only asks
+// whether an optional input is there (a.res, a.x2, a.ws != null), never reads an address.  Non-null, so that an arena offset of
+// 0 still reads as "present"; never dereferenced.
+static char* const kPlanningBase = reinterpret_cast<char*>((uintptr_t)1 << 12);
+
+// The grouped position GEMM of a layer's Winograd form on an input [B,H,W,*] (V -> M): the ConvArgs launch_conv_layer launches and a
+// planner names the op's kernel by (conv_route; there with planning pointers).  *gran / *m_pad: the geometry it was made for.
+inline ConvArgs wino_gemm_args(const ConvLayer& L, int B, int H, int W, float* v, float* m, float* ws, size_t ws_floats, int* gran, long long* m_pad) {
+  int th, tw;
+  long long n_tiles;
+  *gran = wino_gran_for(L, B, H, W);
+  wino_geometry(B, H, W, L.d.dil, &th, &tw, &n_tiles, m_pad, *gran, L.wino_m);
+  ConvArgs g{};
+  g.x = v; g.y = m;
+  g.B = 1; g.H = 1; g.W = (int)std::min<long long>(L.wino_np() * *m_pad, 0x7fffffffLL); g.c1 = L.d.cin; g.c2 = 0; g.Ho = 1; g.Wo = g.W;
+  g.ws = ws; g.ws_floats = ws_floats;
+  g.mt_per_group = (int)(*m_pad / 128); g.w_group_stride = L.wino.rs ? L.wino_group_bytes : L.wino_group_floats;
+  return g;
+}
+// whether launch_conv_layer runs the layer's Winograd form
+inline bool conv_layer_runs_wino(const ConvLayer& L, bool two_sources, bool has_scratch) { return L.has_wino && !two_sources && has_scratch; }
+
 // One conv layer, as Winograd (input transform -> grouped GEMM -> output transform) when the layer carries
 // that form and scratch is supplied, else as the direct kernel.
 // `produced`: what the layer that wrote a.x left behind when it skipped its split-K reduce (common.h: DeferredSplit); consumed here.
 inline int launch_conv_layer(const ConvLayer& L, const ConvArgs& a, float* wino_v, float* wino_m, hipStream_t s, DeferredSplit* produced = nullptr) {
   const bool deferred_in = produced && produced->valid;
-  if (!(L.has_wino && !a.x2 && wino_v && wino_m)) {
+  if (!conv_layer_runs_wino(L, a.x2 != nullptr, wino_v && wino_m)) {
     if (deferred_in) return fail(PEANUT_EINVAL, L.name + ": the producer deferred its split-K reduce to a layer that cannot sum it");
     return launch_conv(L.d, a, s);
   }
-  int th, tw, rc;
-  long long n_tiles, m_pad;
-  const int gran = wino_gran_for(L, a.B, a.H, a.W);
-  wino_geometry(a.B, a.H, a.W, L.d.dil, &th, &tw, &n_tiles, &m_pad, gran, L.wino_m);
-  const long long np = L.wino_np();
-  if (np * m_pad > 0x7fffffffLL) return fail(PEANUT_EINVAL, L.name + ": Winograd problem too large");
+  int gran, rc;
+  long long m_pad;
+  const ConvArgs g = wino_gemm_args(L, a.B, a.H, a.W, wino_v, wino_m, a.ws, a.ws_floats, &gran, &m_pad);
+  if (L.wino_np() * m_pad > 0x7fffffffLL) return fail(PEANUT_EINVAL, L.name + ": Winograd problem too large");
   rc = launch_wino_input(a.x, wino_v, a.B, a.H, a.W, L.d.cin, L.d.dil, s, gran, L.wino_m, 0, deferred_in ? produced : nullptr);
   if (produced) produced->valid = false;
   if (rc) return rc;
-  ConvArgs g{};
-  g.x = wino_v; g.y = wino_m;
-  g.B = 1; g.H = 1; g.W = (int)(np * m_pad); g.c1 = L.d.cin; g.c2 = 0; g.Ho = 1; g.Wo = g.W;
-  g.ws = a.ws; g.ws_floats = a.ws_floats;
-  g.mt_per_group = (int)(m_pad / 128); g.w_group_stride = L.wino.rs ? L.wino_group_bytes : L.wino_group_floats;
   if ((rc = launch_conv(L.wino, g, s))) return rc;
   return launch_wino_output(wino_m, L.d.scale, L.d.shift, a.res, a.y, a.B, a.H, a.W, L.d.cout, L.d.dil, L.d.relu, s, gran, L.wino_m);
 }

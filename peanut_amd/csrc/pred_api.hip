@@ -222,29 +222,41 @@ std::unique_ptr<ConvLayer> build_grouped(const std::vector<ConvLayer*>& parts, c
   return G;
 }
 
-// the kernel symbol family launch_conv will pick (conv_igemm.hip: launch_conv)
-std::string conv_kernel_name(const ConvDesc& d, bool two_source = false, long long M = 0, int mt_per_group = 0, const Act* out = nullptr,
-                             bool has_res = false) {
-  if (out && !two_source && !has_res) {      // conv_patch.hip: the stem's 3x3 convs
-    ConvArgs a{};
-    a.B = out->B; a.Ho = out->H; a.Wo = out->W;
-    if (conv_patch_eligible(d, a)) return conv_patch_kernel_name(d, false);
+// The ConvDesc / ConvArgs of an OP_CONV or OP_WINO_GEMM op: what run_op launches and what build_plan names the op's kernel by (there
+// with base = kPlanningBase: the route reads shapes, sizes and which optional inputs exist, never an address).  scale_rows backs a.group_rows.
+const ConvDesc& conv_op_desc(const Op& op) { return op.kind == OP_WINO_GEMM ? op.conv->wino : op.conv->d; }
+ConvArgs conv_op_args(const peanut_pred* h, const Plan& pl, const Op& op, char* base, int (&scale_rows)[8]) {
+  auto P = [&](const Act& a) { return (float*)((uintptr_t)base + a.off); };
+  ConvArgs a{};
+  a.x = P(op.in); a.y = P(op.out);
+  a.ws = P(op.branch ? pl.splitk2 : pl.splitk); a.ws_floats = kSplitKScratchFloats;
+  if (op.kind == OP_WINO_GEMM) {
+    a.B = 1; a.H = 1; a.W = op.in.W; a.c1 = op.in.C; a.c2 = 0; a.Ho = 1; a.Wo = op.in.W;
+    a.mt_per_group = op.wino_mt_per_group;
+    a.group_valid_rows = op.wino_valid_rows;
+    a.w_group_stride = op.conv->wino.rs ? op.conv->wino_group_bytes : op.conv->wino_group_floats;
+    return a;
   }
-  if (d.rs == 2) return std::string(d.s_planes == 3 ? "conv_rs6_128x" : (d.s_planes == 4 ? "conv_rs3h_128x" : "conv_rs3_128x")) + std::to_string(d.bn_tile);
-  if (d.rs) return gemm_rs_kernel_name(d.cout, M, mt_per_group, d.bn_tile, d.cin, d.s_planes);
-  if (d.bk == 32 && d.kh == 1 && d.kw == 1 && d.pad == 0 && (!two_source || d.stride == 1) && d.cin % 32 == 0 && conv_pw_enabled())
-  {
-    const int flush = d.flush_ch / d.bk;
-    if (conv_pw_uses_256wp(d.cout, M, d.stride, mt_per_group, d.bn_tile, d.cin, 0, flush))
-      return "conv_pw_glds_256x256p";
-    if (conv_pw_uses_ares(d.cin, d.cout, M, d.stride, two_source, flush, d.bn_tile)) return "conv_pw_ares_128x128";
-    if (conv_pw_uses_256w(d.cout, M, mt_per_group, d.bn_tile, d.cin, flush)) return "conv_pw_glds_256x256";
-    if (conv_pw_uses_256p(d.cout, M, mt_per_group, d.bn_tile, d.cin, flush, M * d.stride * d.stride)) return "conv_pw_glds_256x128p";
-    if (conv_pw_uses_256(d.cout, M, mt_per_group, d.bn_tile, d.cin)) return "conv_pw_glds_256x128";
-    if (conv_pw_narrow_tiles(d.cin, d.cout, M, d.bn_tile, mt_per_group)) return "conv_pw_glds_128x64";
-    return "conv_pw_glds_128x" + std::to_string(d.bn_tile);
+  a.x2 = op.has_in2 ? P(op.in2) : nullptr;
+  a.res = op.has_res ? P(op.res) : nullptr;
+  a.B = op.in.B; a.H = op.in.H; a.W = op.in.W;
+  a.c1 = op.in.C; a.c2 = op.has_in2 ? op.in2.C : 0;
+  a.Ho = op.out.H; a.Wo = op.out.W;
+  if (op.group_mt) {     // per-scale PSP convs as one grouped GEMM over [scales * srows, C]
+    // rows of each scale that hold data (B * k^2): the skinny kernel (gemm_skinny.hip) computes only those
+    int most = 0;
+    for (int i = 0; i < 8; ++i) scale_rows[i] = 0;
+    for (int i = 0; i < h->cfg.n_pool_scales && i < 8; ++i) {
+      scale_rows[i] = pl.B * h->cfg.pool_scales[i] * h->cfg.pool_scales[i];
+      most = std::max(most, scale_rows[i]);
+    }
+    a.group_valid_rows = most;
+    a.group_rows = scale_rows;
+    a.mt_per_group = op.group_mt;
+    a.w_group_stride = op.conv->w.bytes / sizeof(float) / (size_t)h->cfg.n_pool_scales;
+    a.ss_group_stride = op.conv->d.cout_pad;
   }
-  return "conv_igemm_128x" + std::to_string(d.bn_tile) + "x" + std::to_string(d.bk);
+  return a;
 }
 
 // One conv layer into the plan.  `ar` is only needed for layers that carry a Winograd form (scratch for the transformed
@@ -269,7 +281,7 @@ void push_conv(Plan& pl, const ConvLayer* L, const Act& in, const Act* in2, cons
     a.wino_gran = gran;
     a.bytes = (double)in.bytes + np * (double)n_tiles * in.C * 4.0;
     pl.ops.push_back(a);
-    Op g; g.kind = OP_WINO_GEMM; g.name = L->name + tag + "gemm]"; g.kernel = conv_kernel_name(L->wino, false, npl * m_pad, (int)(m_pad / 128)); g.conv = L;
+    Op g; g.kind = OP_WINO_GEMM; g.name = L->name + tag + "gemm]"; g.conv = L;
     g.in = v; g.in.W = (int)(npl * m_pad); g.in.C = in.C; g.out = m; g.wino_mt_per_group = (int)(m_pad / 128); g.wino_gran = gran; g.wino_valid_rows = (int)n_tiles;
     g.flops = 2.0 * np * (double)m_pad * L->d.cout * L->cin_real;     // executed, not the direct-form count
     g.bytes = np * (double)m_pad * (in.C * 4.0 + L->d.cout * 4.0) +
@@ -286,7 +298,6 @@ void push_conv(Plan& pl, const ConvLayer* L, const Act& in, const Act* in2, cons
   }
   Op op;
   op.kind = OP_CONV; op.name = L->name; op.conv = L; op.in = in; op.out = out;
-  op.kernel = conv_kernel_name(L->d, in2 != nullptr, (long long)out.B * out.H * out.W, 0, &out, res != nullptr);
   if (in2) { op.in2 = *in2; op.has_in2 = true; }
   if (res) { op.res = *res; op.has_res = true; }
   op.flops = conv_flops(L, out);
@@ -328,7 +339,7 @@ std::unique_ptr<Plan> build_plan(const peanut_pred* h, int B, int H, int W) {
     Act y = make_act(ar, B, conv_out_dim(x.H, d.kh, d.stride, d.pad, d.dil),
                      conv_out_dim(x.W, d.kw, d.stride, d.pad, d.dil), d.cout);
     if (i == 0 && nchw_stem) {
-      Op op; op.kind = OP_CONV_NCHW; op.name = h->stem[0]->name; op.kernel = conv_patch_kernel_name(d, true); op.conv = h->stem[0];
+      Op op; op.kind = OP_CONV_NCHW; op.name = h->stem[0]->name; op.kernel = conv_kernel_family(conv_route_patch_nchw()); op.conv = h->stem[0];
       op.in = x; op.out = y;
       op.flops = conv_flops(h->stem[0], y);
       op.bytes = (double)B * H * W * h->cfg.in_channels * 4.0 + (double)y.bytes + (double)conv_packed_floats(d.cin, d.cout, d.kh, d.kw, d.bn_tile) * 4;
@@ -502,13 +513,6 @@ std::unique_ptr<Plan> build_plan(const peanut_pred* h, int B, int H, int W) {
         if (pl->ops[i].has_res) { pl->ops[i].join_before = true; break; }   // the one consumer of R
       for (const auto& t : side_bufs) rel(t);
     }
-    // the grouped per-scale GEMMs of the pyramid branch run on the skinny kernel at batch 1 (run_op, gemm_skinny.hip)
-    for (size_t i = side_first; i < side_end; ++i) {
-      Op& op = pl->ops[i];
-      if (op.kind == OP_CONV && op.group_mt == 1 && opt(OPT_PW_SKINNY) != 0 && B * kmax * kmax <= 64 &&
-          op.conv->d.bn_tile == 128 && op.conv->d.bk == 32 && op.conv->d.cout % 128 == 0 && (op.conv->d.cin / 32) % 4 == 0)
-        op.kernel = "gemm_skinny";
-    }
     rel(r);
   } else {
     Act up = make_act(ar, B, x.H, x.W, h->cfg.n_pool_scales * h->cfg.head_channels);
@@ -530,6 +534,12 @@ std::unique_ptr<Plan> build_plan(const peanut_pred* h, int B, int H, int W) {
     pl->ops.push_back(op);
   }
   rel(lo);
+  // the kernel family of every conv op: the route launch_conv will take for the ConvArgs run_op will pass (conv_route.hip)
+  for (Op& op : pl->ops) {
+    if (op.kind != OP_CONV && op.kind != OP_WINO_GEMM) continue;
+    int scale_rows[8];
+    op.kernel = conv_kernel_family(conv_route(conv_op_desc(op), conv_op_args(h, *pl, op, kPlanningBase, scale_rows)));
+  }
   return pl;   // pl->bytes (high-water mark) is filled in by get_plan
 }
 
@@ -571,29 +581,8 @@ static int run_op(peanut_pred* h, const Plan& pl, const Op& op, const float* in_
     case OP_CONV_NCHW:
       return launch_conv_patch_nchw(op.conv->d, in_dev, h->cfg.in_channels, P(op.out), pl.B, pl.H, pl.W, op.out.H, op.out.W, s);
     case OP_CONV: {
-      ConvArgs a{};
-      a.x = P(op.in);
-      a.x2 = op.has_in2 ? P(op.in2) : nullptr;
-      a.res = op.has_res ? P(op.res) : nullptr;
-      a.y = P(op.out);
-      a.B = op.in.B; a.H = op.in.H; a.W = op.in.W;
-      a.c1 = op.in.C; a.c2 = op.has_in2 ? op.in2.C : 0;
-      a.Ho = op.out.H; a.Wo = op.out.W;
-      a.ws = P(op.branch ? pl.splitk2 : pl.splitk); a.ws_floats = kSplitKScratchFloats;
-      int scale_rows[8] = {0};
-      if (op.group_mt) {     // per-scale PSP convs as one grouped GEMM over [scales * srows, C]
-        // rows of each scale that hold data (B * k^2): the skinny kernel (gemm_skinny.hip) computes only those
-        int most = 0;
-        for (int i = 0; i < h->cfg.n_pool_scales && i < 8; ++i) {
-          scale_rows[i] = pl.B * h->cfg.pool_scales[i] * h->cfg.pool_scales[i];
-          most = std::max(most, scale_rows[i]);
-        }
-        a.group_valid_rows = most;
-        a.group_rows = scale_rows;
-        a.mt_per_group = op.group_mt;
-        a.w_group_stride = op.conv->w.bytes / sizeof(float) / (size_t)h->cfg.n_pool_scales;
-        a.ss_group_stride = op.conv->d.cout_pad;
-      }
+      int scale_rows[8];
+      ConvArgs a = conv_op_args(h, pl, op, base, scale_rows);
       if (op.defer_ok) a.defer = &h->deferred;
       return launch_conv(op.conv->d, a, s);
     }
@@ -604,14 +593,8 @@ static int run_op(peanut_pred* h, const Plan& pl, const Op& op, const float* in_
       return rc;
     }
     case OP_WINO_GEMM: {
-      ConvArgs a{};
-      a.x = P(op.in); a.y = P(op.out);
-      a.B = 1; a.H = 1; a.W = op.in.W; a.c1 = op.in.C; a.c2 = 0; a.Ho = 1; a.Wo = op.in.W;
-      a.ws = P(op.branch ? pl.splitk2 : pl.splitk); a.ws_floats = kSplitKScratchFloats;
-      a.mt_per_group = op.wino_mt_per_group;
-      a.group_valid_rows = op.wino_valid_rows;
-      a.w_group_stride = op.conv->wino.rs ? op.conv->wino_group_bytes : op.conv->wino_group_floats;
-      return launch_conv(op.conv->wino, a, s);
+      int scale_rows[8];
+      return launch_conv(op.conv->wino, conv_op_args(h, pl, op, base, scale_rows), s);
     }
     case OP_WINO_OUT:
       return launch_wino_output(P(op.in), op.conv->d.scale, op.conv->d.shift, op.has_res ? P(op.res) : nullptr, P(op.out),
@@ -910,7 +893,11 @@ int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, i
   }
   PEANUT_HIP_CHECK(hipEventRecord(ev[0], s));
   for (size_t i = 0; i < pl->ops.size(); ++i) {
-    if ((rc = run_op(h, *pl, pl->ops[i], in_dev, out_dev, apply_sigmoid, s))) return rc;
+    const Op& op = pl->ops[i];
+    if ((rc = run_op(h, *pl, op, in_dev, out_dev, apply_sigmoid, s))) return rc;
+    // the op table names what ran: the family the launch noted is the one the plan was built with
+    if ((op.kind == OP_CONV || op.kind == OP_WINO_GEMM || op.kind == OP_CONV_NCHW) && op.kernel != noted_kernel())
+      return fail(PEANUT_EINVAL, op.name + ": the plan names kernel '" + op.kernel + "' but '" + noted_kernel() + "' ran");
     PEANUT_HIP_CHECK(hipEventRecord(ev[i + 1], s));
   }
   h->probe_events.push_back(std::move(ev));

@@ -310,8 +310,6 @@ void push_rconv(RPlan& pl, Arena& ar, const ConvLayer* L, const Act& in, const A
   if (L->has_wino) L = wino_pick_form(L, in.B, in.H, in.W);
   ROp op;
   op.kind = R_CONV; op.name = L->name; op.conv = L; op.in = in; op.out = out;
-  op.kernel = L->d.rs ? std::string(L->d.rs == 2 ? "conv_rs" : "gemm_rs") + (L->d.s_planes == 3 ? "6" : (L->d.s_planes == 4 ? "3h" : "3"))
-                      : "conv_igemm_128x" + std::to_string(L->d.bn_tile) + "x" + std::to_string(L->d.bk);
   if (res) { op.res = *res; op.has_res = true; }
   op.flops = conv_flops(L, out);
   op.ext_slot = ext_slot;
@@ -330,6 +328,33 @@ void push_rconv(RPlan& pl, Arena& ar, const ConvLayer* L, const Act& in, const A
     }
   }
   pl.ops.push_back(op);
+}
+
+// The ConvArgs of an R_CONV op: what the run loop hands launch_conv_layer (which then puts the caller's own buffers in) and what
+// build_rplan names the op's kernel by (there with base = kPlanningBase: the route reads shapes, sizes and which optional inputs exist, never an address).
+// side: the op runs on the side stream with the side scratch.
+ConvArgs rconv_args(const RPlan& pl, const ROp& op, char* base, bool side) {
+  auto P = [&](const Act& a) { return (float*)((uintptr_t)base + a.off); };
+  ConvArgs a{};
+  a.x = P(op.in);
+  a.res = op.has_res ? P(op.res) : nullptr;
+  a.y = P(op.out);
+  a.B = op.in.B; a.H = op.in.H; a.W = op.in.W; a.c1 = op.in.C; a.c2 = 0; a.Ho = op.out.H; a.Wo = op.out.W;
+  if (op.has_in2) { a.x2 = P(op.in2); a.c2 = op.in2.C; }
+  a.ws = P(side ? pl.splitk_side : pl.splitk); a.ws_floats = side ? kSplitKSideFloats : kSplitKScratchFloats;
+  return a;
+}
+bool rconv_on_side(const RPlan& pl, const ROp& op) { return op.side && pl.splitk_side.bytes != 0; }
+
+// The kernel family of an R_CONV op (conv_route.hip), as peanut_rcnn_probe_front reports it.  An op that runs as Winograd is three
+// launches: "wino+" + the family of its position GEMM.
+std::string rconv_family(const RPlan& pl, const ROp& op) {
+  const ConvArgs a = rconv_args(pl, op, kPlanningBase, rconv_on_side(pl, op));
+  if (!conv_layer_runs_wino(*op.conv, op.has_in2, op.has_wino)) return conv_kernel_family(conv_route(op.conv->d, a));
+  int gran;
+  long long m_pad;
+  const ConvArgs g = wino_gemm_args(*op.conv, a.B, a.H, a.W, nullptr, nullptr, a.ws, a.ws_floats, &gran, &m_pad);
+  return std::string("wino+") + conv_kernel_family(conv_route(op.conv->wino, g));
 }
 
 Act conv_out_act(Arena& ar, const ConvLayer* L, const Act& in) {
@@ -483,6 +508,8 @@ std::unique_ptr<RPlan> build_rplan(const peanut_rcnn* h, int B, int H, int W) {
     pl->ops.back().rpn_level = true;
     rel(t); rel(o); rel(dl);
   }
+  for (ROp& op : pl->ops)
+    if (op.kind == R_CONV) op.kernel = rconv_family(*pl, op);
   size_t hw = pl->splitk.off + Arena::round_up(pl->splitk.bytes);
   if (pl->rpn.on)
     for (const Act* a : {&pl->rpn.v, &pl->rpn.m, &pl->rpn.t_all, &pl->rpn.obj_all, &pl->rpn.dl_all})
@@ -715,19 +742,15 @@ static int rcnn_front_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int 
         break;
       }
       case R_CONV: {
-        ConvArgs a{};
+        const bool on_side = use_side && rconv_on_side(*pl, op);
+        ConvArgs a = rconv_args(*pl, op, base, on_side);
         a.x = IN(op);
-        a.res = op.has_res ? P(op.res) : nullptr;
         a.y = OUT(op);
-        a.B = op.in.B; a.H = op.in.H; a.W = op.in.W; a.c1 = op.in.C; a.c2 = 0; a.Ho = op.out.H; a.Wo = op.out.W;
-        if (op.has_in2) { a.x2 = P(op.in2); a.c2 = op.in2.C; }
-        a.ws = P(pl->splitk); a.ws_floats = kSplitKScratchFloats;
         hipStream_t os = s;
-        if (op.side && use_side) {      // behind everything enqueued so far, next to what follows
+        if (on_side) {      // behind everything enqueued so far, next to what follows
           PEANUT_HIP_CHECK(hipEventRecord(h->ev_fork, s));
           PEANUT_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
           os = h->side;
-          a.ws = P(pl->splitk_side); a.ws_floats = kSplitKSideFloats;
           side_pending = true;
         }
         DeferredSplit* produced = deferred.valid ? &deferred : nullptr;     // (the previous op's, consumed by this one)
@@ -755,6 +778,9 @@ static int rcnn_front_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int 
     if (families) {
       static const char* const kind_names[] = {"rcnn_preprocess", "conv", "maxpool", "fpn_add_upsampled", "subsample2", "wino+rpn_fused"};
       families[op_index] = op.kind == R_CONV ? std::string(op.has_wino ? "wino+" : "") + noted_kernel() : kind_names[op.kind];
+      // the op table names what ran (an op planned for the side stream's smaller scratch is probed on the main one: not compared)
+      if (op.kind == R_CONV && !rconv_on_side(*pl, op) && families[op_index] != op.kernel)
+        return fail(PEANUT_EINVAL, op.name + ": the plan names kernel '" + op.kernel + "' but '" + families[op_index] + "' ran");
     }
     ++op_index;
     if (events) PEANUT_HIP_CHECK(hipEventRecord(events[op_index], s));
