@@ -290,6 +290,35 @@ int peanut_map_mark_agent_batch(int E, float* const* local_maps, int channels, i
  * launches); -1 for a null handle. */
 int peanut_map_debug_launches(peanut_map_t* h);
 
+/* ---- the goal map of the planner inputs (Agent_State.update_goal_map, nav/agent/agent_state.py:418-446) ----
+ * Whether the agent has seen its object, and the goal cells handed to the planner.  Stateless; two launches (the morphology per
+ * 32 x 32 tile in LDS, then one workgroup per episode that forms the flag and marks the goal cell), no host sync.
+ *   S = local_map[cn] > 0                     (the projection keeps the map non-negative, so this is the reference's `> 0` AND makes
+ *                                              its early-out `local_map[cn].sum() != 0` redundant: a zero sum leaves S empty)
+ *   if morph: S eroded n_erode times, then dilated once (also when n_erode = 0); 4-connected cross; cells outside the map are SET
+ *             for the erosion and UNSET for the dilation (scipy.ndimage.binary_erosion(border_value=1) / binary_dilation, which
+ *             is what scikit-image's binary_erosion / binary_dilation call)
+ *   S &= ((((((c4 + c5) + c6) + c7) + c8) + c9) - c[cn]) == 0     fp32, in that order, over the planes 4 .. min(10, channels) - 1
+ *                                                                 (the reference's hard-coded 4:10), AFTER the morphology
+ *   found = any(S);  goal_map = S if found, else zero but for goal_map[goal_r, goal_c] = 1.  detect = 0 (only_explore): always the latter.
+ * local_map: device fp32, `channels` planes of m x m, plane_stride / row_stride in ELEMENTS, column stride 1 -- a view into the
+ * full map is read in place; it is never written.  cn: 4 <= cn < channels.  morph, detect: 0 or 1 (morph = the goal is not a tv).
+ * n_erode: 0..PEANUT_GOAL_MAP_MAX_ERODE (args.goal_erode, 3 in the reference).  goal_r, goal_c in [0, m).  goal_map: device uint8
+ * [m, m], contiguous; found: device int32.  Both are written completely whatever they held.  PEANUT_EINVAL, nothing enqueued: a
+ * null pointer, a value outside the ranges above, strides under which planes or rows would overlap. */
+#define PEANUT_GOAL_MAP_MAX_ERODE 8
+int peanut_goal_map(const float* local_map, int channels, int m, long long plane_stride, long long row_stride, int cn, int morph,
+                    int n_erode, int detect, int goal_r, int goal_c, uint8_t* goal_map, int32_t* found, void* stream);
+/* The same for E episodes (1..PEANUT_MAP_MAX_BATCH) in the same two launches, the episode being a grid dimension: every episode's
+ * goal_map and found[e] are the bits of the single call.  local_maps, goal_maps: HOST arrays of E device pointers; plane_strides,
+ * row_strides: host [E]; params: host [E,6] = (cn, morph, n_erode, detect, goal_r, goal_c) per episode; found: DEVICE int32 [E].
+ * The single call's checks are applied to every episode before anything is enqueued; two episodes whose goal maps overlap
+ * (the byte ranges [goal_map, goal_map + m * m), identical pointers included) are refused too.  One refused episode refuses the
+ * whole call and leaves every output as it was.  Not checked, in either call: a goal_map or found that lies inside a local map or
+ * inside each other -- the outputs are the caller's own buffers, apart from every input. */
+int peanut_goal_map_batch(int E, const float* const* local_maps, int channels, int m, const long long* plane_strides,
+                          const long long* row_strides, const int* params, uint8_t* const* goal_maps, int32_t* found, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Stage 1 -- Mask R-CNN front end (preprocessing + ResNet-FPN backbone + RPN head)
  *

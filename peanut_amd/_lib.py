@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 17    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 18    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -104,6 +104,10 @@ SIGNATURES = {
     "peanut_map_mark_agent_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_int), _P, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "peanut_map_debug_launches": (C.c_int, [_P]),
+    "peanut_goal_map": (C.c_int, [_P, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  _P, _P, _P]),
+    "peanut_goal_map_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_int), C.POINTER(_P), _P, _P]),
     "peanut_preprocess_obs_batch": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P]),
     "peanut_rcnn_create": (C.c_int, [C.POINTER(_P), C.POINTER(RcnnCfgC), C.POINTER(TensorC), C.c_int]),
     "peanut_rcnn_destroy": (None, [_P]),

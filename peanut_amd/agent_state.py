@@ -12,7 +12,12 @@ differences, all on purpose:
   the same discretisation).  ``collision_map`` / ``visited_vis``, which the reference
   reads from ``self.helper`` (the CPU planner's bookkeeping), are attributes here (uint8 HIP tensors, zero until a
   planner writes them);
-* ``update_goal_map`` (:418-446, scikit-image erosion of the goal category) is CPU planner glue and is not here.
+* ``update_goal_map`` (:418-446: whether the goal category is in the local map, after ``goal_erode`` erosions, a dilation and
+  the "no other category claims the cell" mask) and the planner-input dict (:251-257) are here behind ``args.goal_map`` (a
+  peanut_amd-only switch, default off): two launches on the local map where it lies (csrc/goal_map.hip) and a 4-byte read-back
+  instead of a device reduction, a copy of the plane to the host and up to four scikit-image passes there.  ``planner_inputs``
+  is what the reference's ``Agent_Helper.plan_act`` takes; the local planner itself (``_plan``, ``_get_stg``, collision and
+  visited bookkeeping) stays out.
 
 The 12-byte pose read-back per step (`local_pose.cpu()`, :276) is kept: the integer cell indices it
 yields drive the host-side decisions exactly as in the reference.  The eight small tensor operations that follow it
@@ -40,7 +45,7 @@ def default_args(**over):
              frame_height=120, frame_width=160, env_frame_height=480, env_frame_width=640, vision_range=100,
              hfov=79.0, du_scale=1, cat_pred_threshold=5.0, exp_pred_threshold=1.0, map_pred_threshold=0.1,
              camera_height=0.88, min_depth=0.5, max_depth=5.0, sem_pred_prob_thr=0.95, goal_thr=0.985,
-             dist_weight_temperature=500, timestep_limit=499)
+             dist_weight_temperature=500, timestep_limit=499, goal_map=False, goal_erode=3)
     a.update(over)
     return Namespace(**a)
 
@@ -95,6 +100,11 @@ class Agent_State:
         self._goal = None
         self.last_global_goal = None
         self.value_max = None
+        # update_goal_map (agent_state.py:418-446): the goal map stays on the device, found_goal comes back through a pinned word
+        self.goal_map = None
+        self.found_goal = False
+        self._found_dev = None
+        self._found_host = None
 
     # ---- agent_state.py:94-105 ----
     def reset(self):
@@ -102,6 +112,7 @@ class Agent_State:
         self.step = 0
         self.goal_cat = -1
         self.found_goal = False
+        self.goal_map = None
         self.init_map_and_pose()
         self.target_pred = None
         self.last_global_goal = None
@@ -335,6 +346,53 @@ class Agent_State:
             self.last_global_goal = self.global_goals
             self.global_goals = new_global_goal
 
+    # ---- agent_state.py:418-446, on the device ----
+    def update_goal_map(self, infos):
+        """``goal_map`` (uint8 HIP tensor [local_w, local_h], the same buffer on every step) and ``found_goal`` (0 / 1) from the
+        local map where it lies -- contiguous or a view into the full map -- in two launches (``peanut_goal_map``) and one 4-byte
+        read-back.  ``local_map`` is only read."""
+        lm, ps, rs, params = self._goal_map_args(infos)
+        if self._found_dev is None:
+            self._found_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._found_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        with torch.cuda.device(self.device):
+            rc = _lib.load().peanut_goal_map(lm.data_ptr(), int(lm.shape[0]), int(lm.shape[1]), ps, rs, *params, self.goal_map.data_ptr(),
+                                             self._found_dev.data_ptr(), _lib.current_stream_ptr(self.device))
+            _lib.check(rc, "peanut_goal_map")
+            self._found_host.copy_(self._found_dev, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        self.found_goal = int(self._found_host[0])
+
+    def _goal_map_args(self, infos):
+        """What ``peanut_goal_map`` reads of this episode: (local_map, plane stride, row stride, (cn, morph, n_erode, detect, goal_r,
+        goal_c)); allocates ``goal_map`` on first use.  :428-429 (only_explore, cn), :437-438 (no erosion for a tv: too thin)."""
+        args = self.args
+        lm = self.local_map
+        if lm.dtype != torch.float32 or lm.dim() != 3 or lm.shape[1] != lm.shape[2] or lm.stride(2) != 1:
+            raise ValueError(f"update_goal_map: the local map must be a square fp32 [C, M, M] tensor with unit column stride, got "
+                             f"{tuple(lm.shape)} {lm.dtype} strides {tuple(lm.stride())}")
+        if self.goal_map is None:
+            self.goal_map = torch.empty((self.local_w, self.local_h), dtype=torch.uint8, device=self.device)
+        params = (int(self.goal_cat) + 4, int('tv' not in infos.get('goal_name', '')), int(getattr(args, 'goal_erode', 3)),
+                  int(args.only_explore == 0), int(self.global_goals[0][0]), int(self.global_goals[0][1]))
+        return lm, int(lm.stride(0)), int(lm.stride(1)), params
+
+    # ---- agent_state.py:251-257 ----
+    def planner_inputs(self, infos, host=True):
+        """The dict ``update_state`` hands to ``Agent_Helper.plan_act`` in the reference (without ``sem_map_pred``, which is
+        visualisation only).  ``host=True``: NumPy with the reference's dtypes and shapes (obstacle / exp_pred float32 copies,
+        goal float64 0/1, pose_pred a copy); ``host=False``: the same keys as HIP tensors / views, nothing copied."""
+        if self.goal_map is None:
+            raise RuntimeError("planner_inputs needs update_goal_map (args.goal_map) to have run on this step")
+        if not host:
+            return {'obstacle': self.local_map[0], 'exp_pred': self.local_map[1], 'pose_pred': self.planner_pose_inputs,
+                    'goal': self.goal_map, 'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+        return {'obstacle': np.ascontiguousarray(self.local_map[0].cpu().numpy()),
+                'exp_pred': np.ascontiguousarray(self.local_map[1].cpu().numpy()),
+                'pose_pred': self.planner_pose_inputs.copy(),
+                'goal': self.goal_map.cpu().numpy().astype(np.float64),
+                'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+
     # ---- agent_state.py:449-454 ----
     def inc_step(self):
         args = self.args
@@ -346,8 +404,8 @@ class Agent_State:
     def update_state(self, obs, infos):
         """Map update -> (every num_local_steps) full-map update -> (every update_goal_freq steps,
         at step 0, or near the goal) prediction + long-term goal selection (:240-245; ``args.select_goal = False``
-        skips the latter).  Returns whether a prediction ran.  ``update_goal_map`` and the planner-input assembly
-        (:246-263) are CPU planner glue outside the hot path."""
+        skips the latter), then with ``args.goal_map`` on ``update_goal_map`` (:247).  Returns whether a prediction ran; the
+        planner-input dict (:251-257) is ``planner_inputs(infos)``."""
         args = self.args
         self.goal_cat = infos['goal_cat_id']
         self.poses = self._upload_pose(infos['sensor_pose'])
@@ -360,6 +418,8 @@ class Agent_State:
             if select:
                 self.update_global_goal()
             predicted = True
+        if getattr(args, "goal_map", False):
+            self.update_goal_map(infos)
         self.inc_step()
         return predicted
 
@@ -389,6 +449,8 @@ class Agent_State_Group:
     episodes predict on a step with ``select_goal`` on, their long-term goals are selected in ONE batched solve
     (``goal.select_batch``: the launches and synchronisations of one solve instead of E in a row), begun for all of them before
     their prediction forwards; every episode's field, weights and goal are the bits of its own ``update_global_goal``.
+    With ``args.goal_map`` on, the goal maps of all active episodes of a step go through ONE ``peanut_goal_map_batch`` call and ONE
+    ``[E]`` read-back, after every episode's goal of that step is final and before any ``inc_step``.
 
     The states share one ``Semantic_Mapping`` handle, reserved for ``max_batch`` episodes (default: all of them).  The batch
     is ``self.active``, in order; ``drop`` takes an episode out (it ended), ``reset_active`` puts all back."""
@@ -421,6 +483,9 @@ class Agent_State_Group:
         self.batch_predictions = bool(batch_predictions)
         self.batch_goals = bool(batch_goals)
         self.goal_batches = 0              # select_batch calls so far (diagnostics)
+        self.goal_map_batches = 0          # peanut_goal_map_batch calls so far (diagnostics)
+        self._found_dev = None
+        self._found_host = None
         self.sem_map_module = first.sem_map_module
         self.sem_map_module.reserve(max_batch)
         for s in states:
@@ -480,6 +545,27 @@ class Agent_State_Group:
         return select_batch([s._goal_solver() for s in states], [s._goal_inputs() for s in states], [s.target_pred for s in states],
                             float(getattr(args, "dist_weight_temperature", 500)), int(args.map_resolution))
 
+    def _goal_map_batch(self, maps):
+        """``maps``: per episode what ``Agent_State._goal_map_args`` returns plus its goal_map tensor -> one call, one read-back.
+        Returns the E found flags."""
+        E = len(maps)
+        lm0 = maps[0][0]
+        if self._found_dev is None:
+            self._found_dev = torch.zeros(self.max_batch, dtype=torch.int32, device=self.device)
+            self._found_host = torch.zeros(self.max_batch, dtype=torch.int32).pin_memory()
+        ptrs = (C.c_void_p * E)(*[mp[0].data_ptr() for mp in maps])
+        ps = (C.c_longlong * E)(*[mp[1] for mp in maps])
+        rs = (C.c_longlong * E)(*[mp[2] for mp in maps])
+        params = (C.c_int * (6 * E))(*[v for mp in maps for v in mp[3]])
+        outs = (C.c_void_p * E)(*[mp[4].data_ptr() for mp in maps])
+        with torch.cuda.device(self.device):
+            rc = _lib.load().peanut_goal_map_batch(E, ptrs, int(lm0.shape[0]), int(lm0.shape[1]), ps, rs, params, outs,
+                                                   self._found_dev.data_ptr(), _lib.current_stream_ptr(self.device))
+            _lib.check(rc, "peanut_goal_map_batch")
+            self._found_host[:E].copy_(self._found_dev[:E], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+        return [int(v) for v in self._found_host[:E]]
+
     def _predict_batch(self, crops):
         """One prediction forward over the windows of the episodes that predict on this step -> [n,K,W,W]."""
         return self.active[0].prediction_model.get_prediction_batch(torch.cat(crops))
@@ -521,6 +607,22 @@ class Agent_State_Group:
             s.global_goals = [[int(rgoal[0] * s.local_w), int(rgoal[1] * s.local_h)]]
             s.global_goals = [[min(x, int(s.local_w - 1)), min(y, int(s.local_h - 1))] for x, y in s.global_goals]
 
+    def update_goal_maps(self, states, infos):
+        """``Agent_State.update_goal_map`` for the episodes of ``states`` that have ``args.goal_map`` on: one batched call (the
+        episodes may differ in goal category, in the tv rule and in their strides), one read-back."""
+        on = [(s, i) for s, i in zip(states, infos) if getattr(s.args, "goal_map", False)]
+        if not on:
+            return
+        maps = []
+        for s, i in on:
+            mp = s._goal_map_args(i)
+            if tuple(mp[0].shape) != tuple(on[0][0].local_map.shape):
+                raise ValueError("update_goal_maps: the local maps of one batch must have one shape")
+            maps.append(mp + (s.goal_map,))
+        self.goal_map_batches += 1
+        for (s, _), found in zip(on, self._goal_map_batch(maps)):
+            s.found_goal = found
+
     def update_local_maps(self, obs, sensor_poses):
         """``Agent_State.update_local_map`` for every active episode: one pose upload, one projection, one read-back, the
         host decisions per episode, one marking launch."""
@@ -545,8 +647,10 @@ class Agent_State_Group:
         predicted = [False] * E
         batch = self._goal_batch([s for s in act if s._prediction_due()]) if self.batch_goals else []
         if batch:
-            return self._update_state_goal_batch(act, batch)
+            return self._update_state_goal_batch(act, batch, infos)
         if not self.batch_predictions:
+            # the goal maps go through one call after the last episode's goal is final: only then are the step counters held back
+            goal_maps = any(getattr(s.args, "goal_map", False) for s in act)
             for e, s in enumerate(act):
                 s._step_full_map()
                 if s._prediction_due():
@@ -555,7 +659,12 @@ class Agent_State_Group:
                     if select:
                         s.update_global_goal()
                     predicted[e] = True
-                s.inc_step()
+                if not goal_maps:
+                    s.inc_step()
+            if goal_maps:
+                self.update_goal_maps(act, infos)
+                for s in act:
+                    s.inc_step()
             return predicted
         for s in act:
             s._step_full_map()
@@ -568,11 +677,12 @@ class Agent_State_Group:
                 if getattr(act[e].args, "select_goal", True):
                     act[e].update_global_goal()
                 predicted[e] = True
+        self.update_goal_maps(act, infos)
         for s in act:
             s.inc_step()
         return predicted
 
-    def _update_state_goal_batch(self, act, batch):
+    def _update_state_goal_batch(self, act, batch, infos):
         """The rest of ``update_state`` on a step on which the episodes of ``batch`` (>= 2) select their goals in one solve: local
         periods, write-back of the batch's local maps, ONE begin, the prediction forwards (the batch's beside their E fields), the
         single way for the other due episodes, ONE ``select_batch``, the host bookkeeping per episode."""
@@ -608,6 +718,7 @@ class Agent_State_Group:
         self.goal_batches += 1
         for s, res in zip(batch, self._goal_select_batch(batch)):
             s._goal_result(res)
+        self.update_goal_maps(act, infos)
         for s in act:
             s.inc_step()
         return predicted

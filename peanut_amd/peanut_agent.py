@@ -7,7 +7,8 @@ Per step (peanut_agent.py:38-68): pose change from ``gps`` / ``compass`` -> goal
 agent_helper.py:166-195; here the HIP detector / mask accumulation / ``peanut_preprocess_obs``) ->
 ``Agent_State.init_with_obs`` on the first frame -> ``Agent_State.update_state``.  The local FMM planner that turns
 the planner inputs into a motor action (``Agent_Helper.plan_act``, agent_helper.py:130-159) needs the simulator to
-close the loop and is not part of the hot path; ``act`` therefore returns the planner inputs themselves."""
+close the loop and is not part of the hot path; ``act`` therefore returns the planner inputs themselves (with ``args.goal_map``
+on, the reference's whole planner-input dict under ``'planner_inputs'``)."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -23,6 +24,9 @@ from .segmentation import accumulate_instances
 # nav/constants.py:21-31
 hm3d_names = {0: "chair", 1: "bed", 2: "plant", 3: "toilet", 4: "tv_monitor", 5: "sofa"}
 hm3d_to_coco = {0: 0, 1: 3, 2: 2, 3: 4, 4: 5, 5: 1}
+# goal_cat_id (the COCO-side category the maps are indexed by) -> goal_name: the inverse of the two tables above, for drivers that
+# start from the category (replay.run_episode / run_episodes); update_goal_map's tv rule reads the name
+coco_goal_names = {coco: hm3d_names[hm3d] for hm3d, coco in hm3d_to_coco.items()}
 
 
 class PEANUT_Agent:
@@ -98,5 +102,8 @@ class PEANUT_Agent:
             self.first_obs = False
         predicted = self.agent_states.update_state(obs, info)
         st = self.agent_states
-        return {'predicted': bool(predicted), 'sensor_pose': info['sensor_pose'], 'goal_name': info['goal_name'],
-                'pose_pred': st.planner_pose_inputs.copy(), 'global_goals': [list(g) for g in st.global_goals]}
+        out = {'predicted': bool(predicted), 'sensor_pose': info['sensor_pose'], 'goal_name': info['goal_name'],
+               'pose_pred': st.planner_pose_inputs.copy(), 'global_goals': [list(g) for g in st.global_goals]}
+        if getattr(self.args, "goal_map", False):                          # what Agent_Helper.plan_act takes (peanut_agent.py:66)
+            out['planner_inputs'] = st.planner_inputs(info)
+        return out

@@ -11,6 +11,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 from . import dist as pdist
 from .agent_helper import preprocess_obs
 from .agent_state import Agent_State
+from .peanut_agent import coco_goal_names
 from .segmentation import accumulate_instances
 
 
@@ -40,7 +41,7 @@ def run_episode(state: Agent_State, frames: Iterable[Dict], goal_cat: int,
                 sem = accumulate_instances(fr["masks"], fr["classes"], fr["scores"], args.num_sem_categories - 1,
                                            args.sem_pred_prob_thr, args.goal_thr, goal_cat)
             obs = preprocess_obs(fr["rgb"], fr["depth"], sem, args)
-        infos = {"sensor_pose": fr["sensor_pose"], "goal_cat_id": goal_cat}
+        infos = {"sensor_pose": fr["sensor_pose"], "goal_cat_id": goal_cat, "goal_name": coco_goal_names.get(int(goal_cat), "")}
         if i == 0:
             state.init_with_obs(obs, infos)
         predicted = state.update_state(obs, infos)
@@ -109,7 +110,8 @@ def run_episodes(states, episodes, goal_cats, detector=None,
                                                      args.sem_pred_prob_thr, args.goal_thr, goal))
                 sem = torch.stack(sems)
             obs = preprocess_obs_batch(rgb, depth, sem, args)
-        infos = [{"sensor_pose": fr["sensor_pose"], "goal_cat_id": goal} for fr, goal in zip(frames, goals)]
+        infos = [{"sensor_pose": fr["sensor_pose"], "goal_cat_id": goal, "goal_name": coco_goal_names.get(goal, "")}
+                 for fr, goal in zip(frames, goals)]
         if i == 0:
             group.init_with_obs(obs, infos)
         predicted = group.update_state(obs, infos)

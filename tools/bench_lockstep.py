@@ -16,7 +16,14 @@ the two sides alternating (A B A B A B: three repeats each, the spread of the th
       `batch_goals` off as a third column.  In a tree whose package has no `select_batch` (an older commit, for a side-by-side
       run of its library) the sequential sides alone are measured.
 
-    python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only]
+  (d) the goal map of the planner inputs (`goalmap`, --goalmap-only, written to <out>/goalmap.jsonl): on E 480 x 480 local maps with
+      blobs of the goal category and of others, E `peanut_goal_map` calls against one `peanut_goal_map_batch` (device events around a
+      chain of calls, microseconds per step of E episodes), `Agent_State.update_goal_map` E times against one
+      `Agent_State_Group.update_goal_maps` with their read-backs (wall clock), the reference's statements on the same machine as the
+      host baseline (torch sum, `.cpu()`, the scipy chain scikit-image calls; milliseconds per episode), and the lock-step pipeline
+      of (b) with `args.goal_map` off and on.
+
+    python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only] [--goalmap-only]
 
 writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
 of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
@@ -208,6 +215,181 @@ def pipeline(dev, frames=40, repeats=3, batches=BATCHES):
             out[str(E)]["lockstep_single_goals_steps_per_s"] = _spread(t["lockstep_single_goals"])
         print(f"pipeline, E = {E}: {out[str(E)]}", file=sys.stderr, flush=True)
     return out
+
+
+GOALMAP_BATCHES = (1, 4, 8, 16)
+
+
+def _goalmap_maps(dev, n, m=480, seed=7):
+    """n local maps [14, m, m]: per map a few blobs of the goal category (channel 4 + e % 6; every second map holds one large
+    enough to survive three erosions), blobs of other categories over and beside them, values in [2^-10, 1]."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    maps, cns = [], []
+    for e in range(n):
+        lm = np.zeros((14, m, m), np.float32)
+        cn = 4 + e % 6
+        def blob(ch, lo, hi):
+            h, w = rng.randint(lo, hi + 1, size=2)
+            r0, c0 = rng.randint(0, m - h), rng.randint(0, m - w)
+            lm[ch, r0:r0 + h, c0:c0 + w] = rng.uniform(2.0 ** -10, 1.0, size=(h, w))
+        for _ in range(6):
+            blob(cn, 1, 6)
+        if e % 2 == 0:
+            for _ in range(3):
+                blob(cn, 12, 60)
+        for _ in range(8):
+            blob(4 + rng.randint(0, 10), 5, 60)
+        maps.append(torch.from_numpy(lm).to(dev))
+        cns.append(cn)
+    return maps, cns
+
+
+def _goalmap_host(lm, cn, n_erode=3):
+    """The reference's statements (agent_state.py:430-446) on a device map: reduction, copy to the host, the scipy chain."""
+    from scipy import ndimage as ndi
+    if lm[cn].sum() != 0.:
+        temp_goal = lm[cn].cpu().numpy() > 0
+        for _ in range(n_erode):
+            temp_goal = ndi.binary_erosion(temp_goal, border_value=1)
+        temp_goal = ndi.binary_dilation(temp_goal).astype(float)
+        temp_goal *= (torch.sum(lm[4:10], dim=0) - lm[cn]).cpu().numpy() == 0
+        return int(temp_goal.sum() != 0.)
+    return 0
+
+
+def goalmap(dev, calls=500, repeats=3):
+    import ctypes as C
+    from types import SimpleNamespace
+
+    from peanut_amd import _lib
+    from peanut_amd.agent_state import Agent_State, Agent_State_Group, default_args
+    lib = _lib.load()
+    m = 480
+    maps, cns = _goalmap_maps(dev, max(GOALMAP_BATCHES), m)
+    outs = [torch.zeros((m, m), dtype=torch.uint8, device=dev) for _ in maps]
+    found1 = torch.zeros(max(GOALMAP_BATCHES), dtype=torch.int32, device=dev)
+    foundE = torch.zeros(max(GOALMAP_BATCHES), dtype=torch.int32, device=dev)
+    stream = _lib.current_stream_ptr(dev)
+    args = default_args(sem_gpu_id=dev.index, only_explore=0, goal_map=True)
+    states = [Agent_State(args, prediction_model=SimpleNamespace()) for _ in maps]
+    for s, lm, cn in zip(states, maps, cns):
+        s.local_map, s.goal_cat, s.global_goals = lm, cn - 4, [[48, 48]]
+    infos = [{"goal_name": "chair"}] * len(states)
+    recs = []
+    for E in GOALMAP_BATCHES:
+        ptrs = (C.c_void_p * E)(*[t.data_ptr() for t in maps[:E]])
+        ps, rs = (C.c_longlong * E)(*[m * m] * E), (C.c_longlong * E)(*[m] * E)
+        pr = (C.c_int * (6 * E))(*[v for cn in cns[:E] for v in (cn, 1, 3, 1, 48, 48)])
+        op = (C.c_void_p * E)(*[t.data_ptr() for t in outs[:E]])
+        grp = Agent_State_Group(states[:E])
+
+        def single(n):
+            for _ in range(n):
+                for e in range(E):
+                    lib.peanut_goal_map(maps[e].data_ptr(), 14, m, m * m, m, cns[e], 1, 3, 1, 48, 48, outs[e].data_ptr(),
+                                        found1.data_ptr() + 4 * e, stream)
+
+        def batch(n):
+            for _ in range(n):
+                lib.peanut_goal_map_batch(E, ptrs, 14, m, ps, rs, pr, op, foundE.data_ptr(), stream)
+
+        def single_state(n):
+            for _ in range(n):
+                for s, i in zip(states[:E], infos):
+                    s.update_goal_map(i)
+
+        def batch_state(n):
+            for _ in range(n):
+                grp.update_goal_maps(states[:E], infos[:E])
+        single(3)
+        ref_maps = [o.clone() for o in outs[:E]]
+        batch(3)
+        torch.cuda.synchronize()
+        same = all(torch.equal(a, b) for a, b in zip(ref_maps, outs[:E])) and torch.equal(found1[:E], foundE[:E])
+        t = {"single": [], "batch": [], "single_state": [], "batch_state": []}
+        for _ in range(repeats):
+            for name, fn in (("single", single), ("batch", batch)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                fn(calls)
+                e1.record()
+                torch.cuda.synchronize()
+                t[name].append(e0.elapsed_time(e1) / calls * 1e3)
+            for name, fn in (("single_state", single_state), ("batch_state", batch_state)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(calls)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / calls * 1e6)
+        host = []
+        host_found = [_goalmap_host(maps[e], cns[e]) for e in range(E)]
+        for _ in range(repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for e in range(E):
+                _goalmap_host(maps[e], cns[e])
+            host.append((time.perf_counter() - t0) * 1e3)
+        rec = {"section": "goalmap", "E": E, "m": m, "E_single_calls_us": _spread(t["single"]), "one_batched_call_us": _spread(t["batch"]),
+               "E_update_goal_map_us": _spread(t["single_state"]), "one_update_goal_maps_us": _spread(t["batch_state"]),
+               "host_reference_statements_ms": _spread(host), "found": foundE[:E].cpu().tolist(),
+               "batch_bits_equal_single": bool(same), "found_equals_host": foundE[:E].cpu().tolist() == host_found}
+        print(f"goalmap, E = {E}: {rec}", file=sys.stderr, flush=True)
+        recs.append(rec)
+    return recs
+
+
+def goalmap_pipeline(dev, frames=40, repeats=3, batches=(1, 4, 8)):
+    """The lock-step pipeline of `pipeline` with `args.goal_map` off and on, alternating, on ONE set of states (the switch is
+    flipped on their shared args: two sets of states differ by a percent or two through where their maps lie in memory)."""
+    import gc
+
+    from bench_pipeline import synth_episode
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True, goal_map=False)
+    both = {"off": False, "on": True}
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(batches)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    states = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    recs = []
+    for E in batches:
+        goals = [3] * E
+        for name in both:
+            args.goal_map = both[name]
+            run_episodes(states[:E], [ep[:12] for ep in eps[:E]], goals, detector=det)
+        gc.collect()
+        t = {name: [] for name in both}
+        maps, found = {}, []
+        for _ in range(repeats):
+            for name in both:
+                args.goal_map = both[name]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run_episodes(states[:E], eps[:E], goals, detector=det)
+                torch.cuda.synchronize()
+                t[name].append(E * frames / (time.perf_counter() - t0))
+                maps[name] = [s.full_map.clone() for s in states[:E]]
+                found = [int(s.found_goal) for s in states[:E]]
+        same = all(torch.equal(a, b) for a, b in zip(maps["off"], maps["on"]))
+        rec = {"section": "goalmap_pipeline", "E": E, "frames": frames, "goal_map_off_steps_per_s": _spread(t["off"]),
+               "goal_map_on_steps_per_s": _spread(t["on"]), "found_goal_last_step": found,
+               "maps_bit_identical": bool(same)}
+        print(f"goalmap pipeline, E = {E}: {rec}", file=sys.stderr, flush=True)
+        recs.append(rec)
+    return recs
 
 
 def _goal_inputs(dev, n, frames=24, cache=None):
@@ -437,6 +619,7 @@ def main():
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--goal-only", action="store_true", help="the goal section alone")
     ap.add_argument("--pipeline-only", action="store_true", help="the pipeline section alone")
+    ap.add_argument("--goalmap-only", action="store_true", help="the goalmap section alone -> <out>/goalmap.jsonl")
     ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
     ap.add_argument("--goal-inputs", default=None, help="file that keeps the goal section's inputs between processes")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
@@ -450,6 +633,15 @@ def main():
         goal_trace_child(dev, a.goal_trace_child, cache=a.goal_inputs)
         return
     os.makedirs(a.out, exist_ok=True)
+    if a.goalmap_only:
+        recs = goalmap(dev)
+        if not a.no_pipeline:
+            recs += goalmap_pipeline(dev)
+        with open(os.path.join(a.out, "goalmap.jsonl"), "w") as f:
+            for r in recs:
+                r["device"] = torch.cuda.get_device_name(dev)
+                f.write(json.dumps(r) + "\n")
+        return
     rec = {"device": torch.cuda.get_device_name(dev), "batches": list(BATCHES),
            "method": "one process; per E the two sides alternate, three repeats each; spread = min / median / max of the three"}
     pb = tuple(int(b) for b in a.pipeline_batches.split(","))
