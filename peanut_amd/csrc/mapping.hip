@@ -772,37 +772,37 @@ int peanut_map_create(peanut_map_t** out, const peanut_map_cfg* c) {
   P.toilet_ch = 4 + 4;
   if (P.y1 + P.vr > P.M || P.x1 < 0 || P.x1 + P.vr > P.M) return fail(PEANUT_EINVAL, "peanut_map_create: window outside map");
   const size_t N = P.N, cells = (size_t)P.vr * P.vr;
-  PEANUT_HIP_CHECK(hipMalloc(&h->coords, 3 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->pos, 3 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->keys, N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->seg, N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->skeys, N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->sidx, N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->cell_head, cells * P.zb * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->coords, 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->pos, 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->keys, N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->seg, N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->skeys, N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->sidx, N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->cell_head, cells * P.zb * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(h->cell_head, 0xff, cells * P.zb * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->cell_cnt, cells * P.zb * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->cell_cnt, cells * P.zb * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(h->cell_cnt, 0, cells * P.zb * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->cell_fill, cells * P.zb * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->cell_fill, cells * P.zb * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(h->cell_fill, 0, cells * P.zb * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->cell_first, cells * P.zb * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->cell_first, cells * P.zb * sizeof(int)));
   {
     std::vector<int> big(cells * P.zb, 0x7fffffff);
     PEANUT_HIP_CHECK(hipMemcpy(h->cell_first, big.data(), big.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  PEANUT_HIP_CHECK(hipMalloc(&h->cursor, sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->cursor, sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(h->cursor, 0, sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->stats, sizeof(StairStats)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->stats, sizeof(StairStats)));
   {
     const StairStats init = {0u, 0u, 0u, 0u, 0xffffffffu};   // map_view re-arms it after every frame
     PEANUT_HIP_CHECK(hipMemcpy(h->stats, &init, sizeof(init), hipMemcpyHostToDevice));
   }
-  PEANUT_HIP_CHECK(hipMalloc(&h->wts6, 6 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->feat_s, (size_t)P.ncat * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->proj, 2 * P.F * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->wts6, 6 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->feat_s, (size_t)P.ncat * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->proj, 2 * P.F * cells * sizeof(float)));
   PEANUT_HIP_CHECK(hipMemset(h->proj, 0, 2 * P.F * cells * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->view, P.C * cells * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&h->wt, sizeof(WarpT)));
-  if (P.du > 1) PEANUT_HIP_CHECK(hipMalloc(&h->obs_dec, (size_t)P.C * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->view, P.C * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&h->wt, sizeof(WarpT)));
+  if (P.du > 1) PEANUT_HIP_CHECK(dev_alloc(&h->obs_dec, (size_t)P.C * N * sizeof(float)));
   PEANUT_HIP_CHECK(hipDeviceSynchronize());
   *out = h.release();
   return 0;
@@ -915,37 +915,37 @@ int peanut_map_reserve(peanut_map_t* h, int max_batch) {
   MapScratch& b = h->batch;
   const size_t E = (size_t)max_batch, N = P.N, cells = (size_t)P.vr * P.vr, vox = cells * P.zb;
   // every array as peanut_map_create makes it, E times over, with the same initial contents
-  PEANUT_HIP_CHECK(hipMalloc(&b.coords, E * 3 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.pos, E * 3 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.keys, E * N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.seg, E * N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.skeys, E * N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.sidx, E * N * sizeof(unsigned)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.cell_head, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.coords, E * 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.pos, E * 3 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.keys, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.seg, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.skeys, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.sidx, E * N * sizeof(unsigned)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.cell_head, E * vox * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(b.cell_head, 0xff, E * vox * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.cell_cnt, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.cell_cnt, E * vox * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(b.cell_cnt, 0, E * vox * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.cell_fill, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.cell_fill, E * vox * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(b.cell_fill, 0, E * vox * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.cell_first, E * vox * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.cell_first, E * vox * sizeof(int)));
   {
     std::vector<int> big(E * vox, 0x7fffffff);
     PEANUT_HIP_CHECK(hipMemcpy(b.cell_first, big.data(), big.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  PEANUT_HIP_CHECK(hipMalloc(&b.cursor, E * sizeof(int)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.cursor, E * sizeof(int)));
   PEANUT_HIP_CHECK(hipMemset(b.cursor, 0, E * sizeof(int)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.stats, E * sizeof(StairStats)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.stats, E * sizeof(StairStats)));
   {
     std::vector<StairStats> init(E, StairStats{0u, 0u, 0u, 0u, 0xffffffffu});
     PEANUT_HIP_CHECK(hipMemcpy(b.stats, init.data(), E * sizeof(StairStats), hipMemcpyHostToDevice));
   }
-  PEANUT_HIP_CHECK(hipMalloc(&b.wts6, E * 6 * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.feat_s, E * P.ncat * N * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.proj, E * 2 * P.F * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.wts6, E * 6 * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.feat_s, E * P.ncat * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.proj, E * 2 * P.F * cells * sizeof(float)));
   PEANUT_HIP_CHECK(hipMemset(b.proj, 0, E * 2 * P.F * cells * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.view, E * P.C * cells * sizeof(float)));
-  PEANUT_HIP_CHECK(hipMalloc(&b.wt, E * sizeof(WarpT)));
-  if (P.du > 1) PEANUT_HIP_CHECK(hipMalloc(&b.obs_dec, E * P.C * N * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.view, E * P.C * cells * sizeof(float)));
+  PEANUT_HIP_CHECK(dev_alloc(&b.wt, E * sizeof(WarpT)));
+  if (P.du > 1) PEANUT_HIP_CHECK(dev_alloc(&b.obs_dec, E * P.C * N * sizeof(float)));
   PEANUT_HIP_CHECK(hipDeviceSynchronize());
   h->reserved = max_batch;
   return 0;

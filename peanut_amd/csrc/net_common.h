@@ -17,6 +17,18 @@
 
 namespace peanut {
 
+// Every device allocation the library makes for itself goes through here (but conv_igemm.hip's zero page, which is zero-filled
+// on its next line).  With option debug_poison_alloc set, the new memory is
+// filled with 0xFF bytes (NaN as fp32 / fp64, -1 as int, all ones as a key) and the fill has finished before the call returns,
+// so it precedes every later launch on any stream; with the option at 0 this is hipMalloc and nothing else.
+template <class T>
+inline hipError_t dev_alloc(T** p, size_t n) {
+  hipError_t e = hipMalloc((void**)p, n);
+  if (e != hipSuccess || !opt(OPT_DEBUG_POISON_ALLOC)) return e;
+  e = hipMemset(*p, 0xFF, n);
+  return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -24,7 +36,7 @@ struct DevBuf {
   int ensure(size_t n) {
     if (n <= bytes) return 0;
     if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-    hipError_t e = hipMalloc(&p, n);
+    hipError_t e = dev_alloc(&p, n);
     if (e != hipSuccess) return fail(PEANUT_EHIP, std::string("hipMalloc(") + std::to_string(n) + "): " + hipGetErrorString(e));
     bytes = n;
     return 0;

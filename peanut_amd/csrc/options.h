@@ -24,6 +24,7 @@ enum OptionId {
   OPT_RS_CONV, OPT_RS_BN64_MAXK, OPT_RS256_MINK, OPT_RS256_MINTILES, OPT_RS64_MAXK, OPT_RS64_MAXTILES,
   OPT_WINO_M, OPT_WINO_HEAD_M, OPT_WINO6_MAXDIL, OPT_WINO5_MINDIL, OPT_WINO_FLUSH_CH, OPT_WINO_MIN_CIN, OPT_WINO_NARROW_MINPIX, OPT_WINO_SMALL_MAXWG, OPT_DEFER_SPLITK,
   OPT_PPM_OVERLAP, OPT_PPM_GROUPED, OPT_PPM_TERM_ROWS, OPT_PPM_GROUP_ROWS, OPT_RCNN_WINO_M, OPT_RCNN_STEM_S2D, OPT_RCNN_RPN_FUSED, OPT_RCNN_FPN_OVERLAP, OPT_RCNN_RANK_SORT, OPT_RCNN_TOPK_SLICE, OPT_RCNN_NMS_LEVELS, OPT_FMM_LOCAL32, OPT_FMM_MAX_PASSES, OPT_FMM_BLOCKED, OPT_FMM_INNER,
+  OPT_DEBUG_POISON_ALLOC,
   OPT_COUNT
 };
 
@@ -94,6 +95,7 @@ inline const OptionInfo* option_table() {
       {"fmm_max_passes", 24, false, "goal solver: hard ceiling of the second-order ordering passes; they stop as soon as a pass changes nothing (6-10 passes on the agent's 960 x 960 map; peanut_goal_converged reports whether they reached their fixed point)"},
       {"fmm_blocked", 1, false, "goal solver: a wave relaxes its 8 x 8 block of the tile to convergence between workgroup barriers (round 5; 0: one Jacobi sweep of the whole tile per barrier pair)"},
       {"fmm_inner", 48, false, "goal solver: iterations a wave spends on its block before it publishes it (blocked rounds)"},
+      {"debug_poison_alloc", 0, false, "test switch: every device allocation the library makes for itself (workspace arenas, conv / Winograd / split-K scratch, the detector's and the goal solver's buffers, the map projection's arrays, uploaded weights before their copy) is filled with 0xFF bytes straight after hipMalloc -- fp32 / fp64 read NaN, int reads -1, 64-bit keys all ones -- so a kernel that reads a slot nothing wrote shows up as a changed result (tests/test_workspace_gpu.py); 0: allocations stay as the allocator returns them, no extra call"},
   };
   return t;
 }
