@@ -426,3 +426,38 @@ def test_lockstep_episodes_with_batched_goals_equal_those_without(precision, mon
     # every predicting step with >= 2 due episodes went through select_batch, over all of them, and took over its begun fields
     assert calls_a == [d for d in due_a if d >= 2] and len(calls_a) >= 2 and calls_b == []
     assert begun_a == n_a
+
+
+# ---- 8. the other kernels of the round: options fmm_blocked, fmm_local32, fmm_inner ----
+@pytest.mark.parametrize("blocked,local32,inner", [(1, 1, 1), (1, 1, 1024), (1, 0, 48), (1, 0, 1), (1, 0, 1024), (0, 1, 48), (0, 0, 48)], ids=lambda v: str(v))
+def test_solver_variants_batched_equal_alone_bit_for_bit(blocked, local32, inner):
+    """enqueue_rounds_batch (csrc/goal.hip) picks one of four batch kernels as the single solve does -- fmm_round_blocked_batch_kernel
+    or fmm_round_batch_kernel, with the single-precision or the float64 local solve -- and only (blocked, local32) = (1, 1) with 48
+    inner iterations runs above.  Three ragged 250 x 333 episodes (a maze, a room, a walled-in agent) under every other setting:
+    the batch equals the three alone solves on solvers of the same setting bit for bit, twice (the second time on warm round hints
+    and last weights).  That the setting reached the kernels shows against a default solver on the same episodes: the float64
+    local solve, the whole-tile sweep and fmm_inner = 1 give other bits in the maze's field (another schedule lands elsewhere inside
+    stage B's noise threshold); fmm_inner = 1024 only reschedules (a block has converged long before), so there the field equals the
+    default's bit for bit.  The variants pick the default's goals."""
+    from peanut_amd import _lib
+    from peanut_amd.goal import select_batch
+    H, W = 250, 333
+    items = [_case(k, H, W, 80 + e, (5 + 3 * e, 205 + 3 * e, 20 + e, 320 + e), (100 + e, 150 - 7 * e)) for e, k in enumerate(["maze", "room", "walled"])]
+    tps = _tps(3, 200, 300, seed=9)
+    with _lib.default_options(fmm_blocked=blocked, fmm_local32=local32, fmm_inner=inner):
+        batch, alone = _solvers(3, H, W, 3), _solvers(3, H, W, 3)
+    for rep in range(2):
+        got = select_batch(batch, items, tps, 500.0, RES, want_dist=True, want_value=True)
+        ref = _alone(alone, items, tps, 500.0, want_dist=True, want_value=True)
+        _assert_same(got, ref, f"blocked={blocked} local32={local32} inner={inner} rep {rep}")
+    assert torch.isinf(ref[2]["dist"]).sum().item() >= H * W - 1          # the walled-in agent reaches nothing
+    base = _alone(_solvers(3, H, W, 3), items, tps, 500.0, want_dist=True, want_value=True)
+    differs = int((ref[0]["dist"] != base[0]["dist"]).sum().item())
+    print(f"blocked={blocked} local32={local32} inner={inner}: rounds alone {[r['rounds'] for r in ref]} batch {got[0]['rounds']}, default "
+          f"{[r['rounds'] for r in base]}; {differs} cells of the maze's field differ from the default's in some bit")
+    assert [r["goal"] for r in ref] == [r["goal"] for r in base]
+    assert torch.equal(torch.isfinite(ref[0]["dist"]), torch.isfinite(base[0]["dist"]))
+    if not local32 or not blocked or inner == 1:
+        assert differs > 0, "the default kernels' field, bit for bit"
+    else:
+        assert differs == 0

@@ -671,3 +671,105 @@ def test_selection_is_deterministic():
             first, v0 = key, got["value"]
         assert key == first
         assert torch.equal(got["value"], v0)
+
+
+# ---- the solver's other kernels: options fmm_blocked, fmm_local32, fmm_inner ----
+# enqueue_rounds (csrc/goal.hip) launches one of four instantiations per stage: fmm_round_blocked_kernel or fmm_round_kernel,
+# each with the single-precision or the float64 local solve.  Everything above runs (blocked, local32) = (1, 1) with 48 inner
+# iterations; here every pair runs, and the blocked kernels also with 1 and 1024 inner iterations (the ends of the option's range).
+FMM_VARIANTS = [(1, 1, 48), (1, 1, 1), (1, 1, 1024), (1, 0, 48), (1, 0, 1), (1, 0, 1024), (0, 1, 48), (0, 0, 48)]
+VARIANT_SHAPES = [((250, 333), 23), ((64, 40), 4), ((31, 33), 24), ((7, 300), 25)]
+
+
+def _variant_solver(h, w, blocked, local32, inner):
+    from peanut_amd import _lib
+    from peanut_amd.goal import GeodesicSolver
+    with _lib.default_options(fmm_blocked=blocked, fmm_local32=local32, fmm_inner=inner):
+        return GeodesicSolver(h, w, 0)
+
+
+def _variant_solve(sol, trav, src, gm):
+    """-> [(field, rounds, passes)] of the two solves: one goal cell, a goal mask of several seeds."""
+    out = []
+    for goal, mask in ((src, None), (None, gm)):
+        u = sol.distance(torch.from_numpy(trav), goal=goal, goal_mask=None if mask is None else torch.from_numpy(mask)).cpu().numpy()
+        assert sol.converged
+        out.append((u, sol.rounds, sol.passes))
+    return out
+
+
+@pytest.fixture(scope="module")
+def variant_cases():
+    """shape -> (map, goal cell, goal mask, seed sets of the two solves, their oracle fields, the default solver's two solves): made
+    once for the module, before any variant runs, and read-only from then on."""
+    cases = {}
+    for shape, seed in VARIANT_SHAPES:
+        h, w = shape
+        trav = _maze(h, w, seed)
+        rng = np.random.RandomState(seed)
+        src = (h // 2, w // 2 - 1)
+        trav[max(src[0] - 2, 0):src[0] + 3, max(src[1] - 2, 0):src[1] + 3] = 1
+        gm = np.zeros((h, w), np.uint8)
+        gm[rng.randint(0, h, 4), rng.randint(0, w, 4)] = 1
+        gm[src] = 0
+        ys, xs = np.nonzero(gm)
+        trav[ys[0], xs[0]] = 0                              # a goal on a masked cell
+        seeds = [np.zeros((h, w), bool), gm == 1]
+        seeds[0][src] = True
+        refs = [_oracle_field(trav, list(zip(*np.nonzero(s)))) for s in seeds]
+        base = _variant_solve(_variant_solver(h, w, 1, 1, 48), trav, src, gm)
+        for a in [trav, gm] + seeds + refs + [u for u, _, _ in base]:
+            a.setflags(write=False)
+        cases[shape] = (trav, src, gm, seeds, refs, base)
+    return cases
+
+
+@pytest.mark.parametrize("blocked,local32,inner", FMM_VARIANTS, ids=lambda v: str(v))
+@pytest.mark.parametrize("shape", [s for s, _ in VARIANT_SHAPES], ids=lambda v: "x".join(map(str, v)))
+def test_fmm_solver_variants_meet_the_gates_of_the_default(variant_cases, shape, blocked, local32, inner):
+    """Every (fmm_blocked, fmm_local32) instantiation of the relaxation round, and fmm_inner = 1 / 48 / 1024 on the blocked ones, on
+    maps whose tile edges are ragged (32 x 32 tiles: 250 x 333, 64 x 40, 31 x 33, 7 x 300): the field within FIELD_TOL of the
+    heap-ordered oracle, the fixed point of its own scheme to FIXED_POINT_GATE, and finite on exactly the cells the oracle reaches
+    and the seeds' 4-connected components hold -- one goal cell and a goal mask with a seed on a masked cell.
+
+    Which kernel ran shows in the solve itself, on the 250 x 333 map's goal-cell field: the whole-tile sweep (fmm_blocked = 0), one
+    inner iteration per round (fmm_inner = 1) and the float64 local solve (fmm_local32 = 0) each return a field that differs from the
+    default's in the last bits of most cells (another schedule lands elsewhere inside stage B's noise threshold), and the float64 solve
+    sits at its own fixed point to 1e-8 cell -- out of reach of an increment computed in single precision (2^-24 of a step of about
+    one cell is 6e-8).  The number of rounds is printed, not asserted: the sweep needs exactly the default's 44 here.  fmm_inner = 1024
+    only lets a wave iterate longer before it publishes its block; on these maps a block has converged long before, the field equals
+    the default's bit for bit (asserted), and the case holds that setting to the same gates: the option only reschedules.
+
+    fmm_local32 = 0: its distance to the oracle is printed next to the default's and must not be larger (up to the oracle's own
+    float64 rounding, 1e-9 cell)."""
+    from scipy import ndimage as ndi
+    from oracle import goal_ref
+    h, w = shape
+    trav, src, gm, seeds, refs, base = variant_cases[shape]
+    got = _variant_solve(_variant_solver(h, w, blocked, local32, inner), trav.copy(), src, gm.copy())
+    for k, ((u, rounds, passes), (u0, rounds0, passes0), ref, sd) in enumerate(zip(got, base, refs, seeds)):
+        what = f"{h}x{w} blocked={blocked} local32={local32} inner={inner} {'goal cell' if k == 0 else 'goal mask'}"
+        labels, _ = ndi.label((trav != 0) | sd)
+        reach = np.isin(labels, np.unique(labels[sd]))
+        assert np.array_equal(np.isfinite(u), reach), f"{what}: reached cells = the seeds' components"
+        assert np.array_equal(np.isinf(u), np.isinf(ref)) and np.array_equal(np.isinf(u), np.isinf(u0)), f"{what}: reached cells"
+        assert (u[sd] == 0).all()
+        fin = np.isfinite(ref)
+        err, err0 = float(np.abs(u[fin] - ref[fin]).max()), float(np.abs(u0[fin] - ref[fin]).max())
+        res, _ = goal_ref.fmm_fixed_point_residual(u, trav, sd)
+        print(f"{what}: max |GPU - oracle| {err:.3e} cells (default solver {err0:.3e}), fixed-point residual {float(res.max()):.3e}, "
+              f"{rounds} rounds in {passes} passes (default {rounds0} in {passes0}), "
+              f"{int((u[fin] != u0[fin]).sum())} of {int(fin.sum())} cells differ from the default's in some bit")
+        assert err <= FIELD_TOL, what
+        assert float(res.max()) <= FIXED_POINT_GATE, what
+        if not local32:
+            assert err <= err0 + 1e-9, f"{what}: the float64 local solve is further from the oracle than the single-precision one"
+        if shape == (250, 333) and k == 0:
+            differs = int((u[fin] != u0[fin]).sum())
+            if not local32:
+                assert differs > 0, f"{what}: the float64 local solve returned the single-precision field"
+                assert float(res.max()) <= 1e-8, f"{what}: a fixed-point residual of {float(res.max()):.3e} is no float64 local solve"
+            elif not blocked or inner == 1:
+                assert differs > 0, f"{what}: the default kernel's field, bit for bit"
+            else:
+                assert differs == 0, f"{what}: {differs} cells differ from the default's"
