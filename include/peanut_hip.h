@@ -608,6 +608,79 @@ int peanut_goal_select_batch(int E, peanut_goal_t* const* g, const float* const*
                              double* const* dist_out, double* const* value_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The local planner's short-term goal (ABI 19): Agent_Helper._get_stg (nav/agent/agent_helper.py:374-493) and
+ * FMMPlanner.get_short_term_goal (nav/agent/utils/fmm_planner.py:77-116), the heavy part of every agent step.  The reference does
+ * it on the host: two scikit-image dilations, a scikit-fmm solve on the (m + 2)^2 padded grid, an 11 x 11 window pick, and up to
+ * nine further solves when planning fails.  Here the masks and the pick are three kernels (csrc/stg.hip) around the solver above,
+ * which is used as it is; the host reads back one small struct per solve.  scale == 1 only (the agent's value).
+ * The scalar state machine around it (collision bookkeeping, action choice, untrap: _plan :228-371) is the caller's.
+ * ---------------------------------------------------------------------------------------- */
+#define PEANUT_STG_MAX_RAD 16     /* largest dilation radius (collision disk and goal disk) */
+#define PEANUT_STG_MAX_STEP 5     /* largest step_size: the (2 step + 1)^2 masks travel in the kernel-argument block */
+/* what get_short_term_goal returns, as the window kernel writes it to DEVICE memory */
+typedef struct {
+  double distance;                /* the field at the agent's cell (subset[du, du]) */
+  int32_t stg_r, stg_c;           /* the chosen cell in the coordinates of the field (stg_x + state[0] - du, ...) */
+  int32_t stop, replan;           /* distance < 5.0; the window's minimum > -0.0001 */
+} peanut_stg_window_t;
+/* what _get_stg returns, with how it got there (HOST) */
+typedef struct {
+  double stg_x, stg_y;            /* local-map cells: the `- 1` of :491 applied (x1 = y1 = 0) */
+  double distance;
+  int32_t stop, replan;           /* of the last solve */
+  int32_t retried;                /* 1: the first solve asked to replan and the eroded map was solved (:443-469); with only_explore
+                                   * the caller's next_preset_goal() (:444-445) is due */
+  int32_t n_magnify, n_solves;    /* goal dilations of the "make the goal larger" loop (:473-489); solves in all */
+  int32_t reserved;
+} peanut_stg_result_t;
+/* The planner's traversible map (:377-420; erode = 1: the retry's, :448-461).  obstacle: device fp32 [m, m] with `row_stride`
+ * elements between rows (local_map[0] may be a view), read in place.  Obstacle bit = rint(v) != 0; then the four border rules as
+ * the reference writes them -- lmb = {gx1, gx2, gy1, gy2}: gx2 == full_w sets the last row, gy2 == full_h the last column,
+ * gx1 == 0 row 0 and gy1 == 0 ROW 0 again (the reference's `grid[y1] = 1`); erode: one 4-connected erosion of that grid with
+ * cells outside it counting as set (scipy's binary_erosion(border_value=1), which scikit-image calls); then
+ * ~dilate(grid, disk(col_rad)), cells outside counting as unset; collision == 1 -> 0, then visited == 1 -> 1, both device uint8
+ * [full_w, full_h] read at offset (gx1, gy1) (either may be NULL: no override); then the 3 x 3 block around (start_r, start_c) -> 1 with
+ * Python's slice semantics: clipped at the far edge, EMPTY along an axis whose start is 0 (`[-1:2]`).  trav_out: device uint8
+ * [(m + 2), (m + 2)], the map offset by one cell inside a ring of 1 (add_boundary).  col_rad <= PEANUT_STG_MAX_RAD, m >= 3,
+ * 0 <= start < m.  No synchronisation. */
+int peanut_stg_traversible(const float* obstacle, long long row_stride, int m, int full_w, int full_h, const int lmb[4], int col_rad,
+                           int erode, const uint8_t* collision, const uint8_t* visited, int start_r, int start_c, uint8_t* trav_out,
+                           void* stream);
+/* The goal cells (:421, 425-435, 481-484): mask_in device uint8, non-zero = goal -- the [m, m] goal map (in_is_padded = 0: a ring
+ * of 0 is added, add_boundary(goal, value=0)) or an already padded [(m + 2), (m + 2)] mask (in_is_padded = 1: the magnify loop) --
+ * dilated by disk(radius) inside the padded grid, cells outside it unset; the dilation may spill into the ring, as in the
+ * reference.  goal_out: device uint8 [(m + 2), (m + 2)] of 0 / 1, not mask_in.  0 <= radius <= PEANUT_STG_MAX_RAD. */
+int peanut_stg_goal(const uint8_t* mask_in, int in_is_padded, int m, int radius, uint8_t* goal_out, void* stream);
+/* HOST only, touches no device: get_mask / get_dist (fmm_planner.py:8-36) for scale 1 and the fractional parts (sx, sy) of the
+ * state, operation by operation in the reference's order with std::pow for `** 2` and `** 0.5` (CPython's float power is libm's
+ * pow).  mask_out, dist_out: host double [(2 step_size + 1)^2]. */
+int peanut_stg_masks(double sx, double sy, int step_size, double* mask_out, double* dist_out);
+/* get_short_term_goal (:77-116) on a device field: field device double [n, n], state = (state_r, state_c) with 0 <= int(state) < n.
+ * The (2 step_size + 1)^2 window at int(state), cells beyond the field = n^2 (np.pad), the reference's arithmetic in double and in
+ * its order, np.argmin's semantics (first occurrence, the first NaN wins).  One workgroup; the masks are computed on the host
+ * (peanut_stg_masks) and passed by value.  result_dev: DEVICE peanut_stg_window_t.  No synchronisation. */
+int peanut_stg_window(const double* field, int n, double state_r, double state_c, int step_size, peanut_stg_window_t* result_dev,
+                      void* stream);
+/* _get_stg whole.  The handle owns the padded masks, the field and a peanut_goal_t of (m + 2) x (m + 2); every solve is
+ * peanut_fmm_distance (goal_mask, fill_mode 1) on the two masks, bit for bit. */
+typedef struct peanut_stg peanut_stg_t;
+int peanut_stg_create(peanut_stg_t** out, int m, int full_w, int full_h, int col_rad, int step_size);
+void peanut_stg_destroy(peanut_stg_t* h);
+/* First solve with the goal dilated by disk(found_goal == 1 ? radius_found : 2) (radius_found: 8, 6 for a toilet); if it asks to
+ * replan, the eroded traversible map and a second solve on the same goal; if found_goal == 1 and distance > magnify_when_hard:
+ * while distance > 100 and the step count <= max_magnify (8, 2 for a toilet), the current padded goal dilated by disk(2) and
+ * solved again on the current traversible map.  obstacle / collision / visited / lmb / start as peanut_stg_traversible
+ * (start_exact = the agent's position in local-map cells, :264-266; the window's state is start_exact + 1); goal_map device uint8
+ * [m, m].  result_out: HOST.  trav_out / goal_out / dist_out: optional device taps ([(m + 2)^2] uint8, uint8, double) of the LAST
+ * solve's masks and field.  Synchronises (the loop conditions are host decisions on the struct read back).  PEANUT_EINVAL with
+ * nothing enqueued and no output touched: a null pointer, m < 2 step_size + 1, lmb not an m x m window inside the full map,
+ * start_exact outside [0, m) on either axis (the reference asserts or wraps there), a radius above PEANUT_STG_MAX_RAD, row_stride < m. */
+int peanut_stg_plan(peanut_stg_t* h, const float* obstacle, long long row_stride, const uint8_t* goal_map, const uint8_t* collision,
+                    const uint8_t* visited, const int lmb[4], const double start_exact[2], int found_goal, int radius_found,
+                    double magnify_when_hard, int max_magnify, peanut_stg_result_t* result_out, uint8_t* trav_out, uint8_t* goal_out,
+                    double* dist_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU: collation of the predicted maps for logging.  One process per GPU, maps /
  * episodes sharded with no data-path collective -- the reference shards by hand with --start_ep/--end_ep/
  * --sem_gpu_id (nav/arguments.py:15-20, nav/collect.py:37-50) and never communicates; this all-gather is the one

@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 18    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 19    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -61,6 +61,17 @@ class RcnnCfgC(C.Structure):
         ("roi_bbox_weights", C.c_float * 4), ("score_thresh_test", C.c_float), ("nms_thresh_test", C.c_float),
         ("detections_per_image", C.c_int), ("mask_threshold", C.c_float),
     ]
+
+
+class StgWindowC(C.Structure):
+    """peanut_stg_window_t: what the window kernel writes to device memory (24 bytes)."""
+    _fields_ = [("distance", C.c_double), ("stg_r", C.c_int32), ("stg_c", C.c_int32), ("stop", C.c_int32), ("replan", C.c_int32)]
+
+
+class StgResultC(C.Structure):
+    """peanut_stg_result_t: what peanut_stg_plan returns on the host."""
+    _fields_ = [("stg_x", C.c_double), ("stg_y", C.c_double), ("distance", C.c_double), ("stop", C.c_int32), ("replan", C.c_int32),
+                ("retried", C.c_int32), ("n_magnify", C.c_int32), ("n_solves", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TensorC(C.Structure):
@@ -149,6 +160,15 @@ SIGNATURES = {
     "peanut_goal_select_batch": (C.c_int, [C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int),
                                            C.POINTER(C.c_int), C.POINTER(_P), C.c_double, C.c_int, C.POINTER(C.c_int),
                                            C.POINTER(C.c_double), C.POINTER(_P), C.POINTER(_P), _P]),
+    "peanut_stg_traversible": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int * 4), C.c_int, C.c_int, _P, _P,
+                                         C.c_int, C.c_int, _P, _P]),
+    "peanut_stg_goal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "peanut_stg_masks": (C.c_int, [C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "peanut_stg_window": (C.c_int, [_P, C.c_int, C.c_double, C.c_double, C.c_int, _P, _P]),
+    "peanut_stg_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "peanut_stg_destroy": (None, [_P]),
+    "peanut_stg_plan": (C.c_int, [_P, _P, C.c_longlong, _P, _P, _P, C.POINTER(C.c_int * 4), C.POINTER(C.c_double * 2), C.c_int, C.c_int,
+                                  C.c_double, C.c_int, C.POINTER(StgResultC), _P, _P, _P, _P]),
     "peanut_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_destroy": (None, [_P]),

@@ -16,8 +16,10 @@ differences, all on purpose:
   the "no other category claims the cell" mask) and the planner-input dict (:251-257) are here behind ``args.goal_map`` (a
   peanut_amd-only switch, default off): two launches on the local map where it lies (csrc/goal_map.hip) and a 4-byte read-back
   instead of a device reduction, a copy of the plane to the host and up to four scikit-image passes there.  ``planner_inputs``
-  is what the reference's ``Agent_Helper.plan_act`` takes; the local planner itself (``_plan``, ``_get_stg``, collision and
-  visited bookkeeping) stays out.
+  is what the reference's ``Agent_Helper.plan_act`` takes;
+* of the local planner, ``_get_stg`` (agent_helper.py:374-493) is here as ``short_term_goal`` behind ``args.plan_stg`` (default
+  off, needs ``args.goal_map``; csrc/stg.hip through ``peanut_amd.planner.ShortTermGoal``); the scalar state machine around it
+  (``_plan``: collision and visited bookkeeping, action choice, untrap) stays out.
 
 The 12-byte pose read-back per step (`local_pose.cpu()`, :276) is kept: the integer cell indices it
 yields drive the host-side decisions exactly as in the reference.  The eight small tensor operations that follow it
@@ -45,7 +47,8 @@ def default_args(**over):
              frame_height=120, frame_width=160, env_frame_height=480, env_frame_width=640, vision_range=100,
              hfov=79.0, du_scale=1, cat_pred_threshold=5.0, exp_pred_threshold=1.0, map_pred_threshold=0.1,
              camera_height=0.88, min_depth=0.5, max_depth=5.0, sem_pred_prob_thr=0.95, goal_thr=0.985,
-             dist_weight_temperature=500, timestep_limit=499, goal_map=False, goal_erode=3)
+             dist_weight_temperature=500, timestep_limit=499, goal_map=False, goal_erode=3, plan_stg=False,
+             magnify_goal_when_hard=100)
     a.update(over)
     return Namespace(**a)
 
@@ -105,6 +108,10 @@ class Agent_State:
         self.found_goal = False
         self._found_dev = None
         self._found_host = None
+        # the local planner's short-term goal (agent_helper.py:374-493), behind args.plan_stg
+        self._stg = None
+        self.stg = None
+        self.stg_stop = None
 
     # ---- agent_state.py:94-105 ----
     def reset(self):
@@ -392,6 +399,28 @@ class Agent_State:
                 'pose_pred': self.planner_pose_inputs.copy(),
                 'goal': self.goal_map.cpu().numpy().astype(np.float64),
                 'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+
+    # ---- agent_helper.py:256-266 + 374-493, on the device ----
+    def short_term_goal(self, infos):
+        """What ``Agent_Helper._plan`` gets from ``_get_stg`` on this step's planner inputs: ((stg_x, stg_y), stop), from
+        ``local_map[0]``, ``goal_map``, ``collision_map``, ``visited_vis``, ``lmb`` and the pose where they lie on the device
+        (``peanut_stg_plan``); ``start_exact`` as ``_plan`` forms it (:264-266).  Needs ``update_goal_map`` to have run on this
+        step.  The whole result stays in ``self._stg.last``."""
+        if not getattr(self.args, "plan_stg", False):
+            raise RuntimeError("short_term_goal is behind args.plan_stg (default off)")
+        if self.goal_map is None:
+            raise RuntimeError("short_term_goal needs update_goal_map (args.goal_map) to have run on this step")
+        if self._stg is None:
+            from .planner import ShortTermGoal
+            self._stg = ShortTermGoal(self.args, device=self.device)
+        args = self.args
+        start_x, start_y, _, gx1, gx2, gy1, gy2 = self.planner_pose_inputs
+        lmb = [int(gx1), int(gx2), int(gy1), int(gy2)]
+        r, c = start_y, start_x
+        start_exact = [r * 100.0 / args.map_resolution - lmb[0], c * 100.0 / args.map_resolution - lmb[2]]
+        self.stg, self.stg_stop = self._stg.get_stg(self.local_map[0], self.goal_map, self.collision_map, self.visited_vis, lmb, start_exact,
+                                                    self.found_goal, infos['goal_name'])
+        return self.stg, self.stg_stop
 
     # ---- agent_state.py:449-454 ----
     def inc_step(self):

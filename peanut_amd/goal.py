@@ -396,3 +396,11 @@ class FMMPlanner():
         (stg_x, stg_y) = np.unravel_index(np.argmin(subset), subset.shape)
         replan = bool(subset[stg_x, stg_y] > -0.0001)
         return (stg_x + state[0] - self.du) * scale, (stg_y + state[1] - self.du) * scale, distance, stop, replan
+
+    def get_short_term_goal_dev(self, state):
+        """The same five values from the device field where it lies (``peanut_stg_window``, csrc/stg.hip): no copy of the field, no
+        ``np.pad``; one 24-byte read-back."""
+        from .planner import stg_window
+        if self.fmm_dist_dev is None:
+            raise RuntimeError("get_short_term_goal_dev needs set_goal / set_multi_goal first")
+        return stg_window(self.fmm_dist_dev, state, self.step_size)

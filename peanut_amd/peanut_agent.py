@@ -8,7 +8,8 @@ agent_helper.py:166-195; here the HIP detector / mask accumulation / ``peanut_pr
 ``Agent_State.init_with_obs`` on the first frame -> ``Agent_State.update_state``.  The local FMM planner that turns
 the planner inputs into a motor action (``Agent_Helper.plan_act``, agent_helper.py:130-159) needs the simulator to
 close the loop and is not part of the hot path; ``act`` therefore returns the planner inputs themselves (with ``args.goal_map``
-on, the reference's whole planner-input dict under ``'planner_inputs'``)."""
+on, the reference's whole planner-input dict under ``'planner_inputs'``; with ``args.plan_stg`` on, also what ``_plan`` gets from
+``_get_stg`` on them, under ``'stg'`` and ``'stop'``: ``Agent_State.short_term_goal``)."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -106,4 +107,8 @@ class PEANUT_Agent:
                'pose_pred': st.planner_pose_inputs.copy(), 'global_goals': [list(g) for g in st.global_goals]}
         if getattr(self.args, "goal_map", False):                          # what Agent_Helper.plan_act takes (peanut_agent.py:66)
             out['planner_inputs'] = st.planner_inputs(info)
+        if getattr(self.args, "plan_stg", False):                          # what _plan gets from _get_stg (agent_helper.py:323)
+            if not getattr(self.args, "goal_map", False):
+                raise ValueError("args.plan_stg needs args.goal_map (the short-term goal reads the goal map)")
+            out['stg'], out['stop'] = st.short_term_goal(info)
         return out
