@@ -428,7 +428,7 @@ int peanut_rcnn_inference(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int H
  * the 28 x 28 mask probabilities (same arithmetic as peanut_paste_masks), so the [n,H,W] instance masks are never
  * materialised.  semantic: device float [B,H,W,n_cats+1] (channel n_cats stays 0, as in the reference);
  * goal_cat_host: HOST int32 [B] (-1 = no goal gate) or NULL.  masks may be NULL (the usual case); the other outputs
- * are those of peanut_rcnn_inference. */
+ * are those of peanut_rcnn_inference.  Synchronises the stream once, as that call does (to read the detection counts). */
 int peanut_rcnn_semantic(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int H, int W, int n_cats, float sem_pred_prob_thr,
                          float goal_thr, const int32_t* goal_cat_host, float* semantic, int* n_det_host, float* boxes,
                          float* scores, int32_t* classes, uint8_t* masks, void* stream);
