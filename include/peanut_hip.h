@@ -679,6 +679,52 @@ int peanut_stg_plan(peanut_stg_t* h, const float* obstacle, long long row_stride
                     const uint8_t* visited, const int lmb[4], const double start_exact[2], int found_goal, int radius_found,
                     double magnify_when_hard, int max_magnify, peanut_stg_result_t* result_out, uint8_t* trav_out, uint8_t* goal_out,
                     double* dist_out, void* stream);
+/* The short-term goals of the episodes of a lock-step group (ABI 20): _get_stg of up to PEANUT_STG_MAX_BATCH episodes, each with
+ * its own peanut_stg_t, in the launches and host synchronisations of the LONGEST chain among them.  Every episode is the state
+ * machine of peanut_stg_plan (first solve, the eroded retry if it asks to replan, the magnify steps) under exactly its conditions;
+ * the call runs in waves: every unfinished episode prepares the masks of its next solve (the traversible maps of a wave in one
+ * launch, the grown goals in one), one batched solve of the solver above follows (a relaxation round is one launch over
+ * (tiles, E), csrc/goal.hip), one window launch over the episodes, one read-back of the [E] window structs and one
+ * synchronisation; the host then advances each episode.  The number of waves is the largest n_solves of the batch, not the sum
+ * (peanut_stg_waves).  The window masks (start_exact is fixed for the call) go up once per call through a pinned table; nothing is
+ * allocated and no stream is made per wave (the tables belong to the first handle, made on its first batch).  Every episode gets,
+ * bit for bit, the result struct and the taps peanut_stg_plan gives on its handle alone, whatever the handles were used for
+ * before; E = 1 equals peanut_stg_plan.
+ * Arguments as a descriptor: `size` = sizeof(peanut_stg_batch_t) first, so that a caller built against another layout is refused.
+ * All arrays are HOST arrays of E entries: h the handles; obstacle / goal_map / collision / visited device pointers and row_stride,
+ * found_goal, radius_found, magnify_when_hard, max_magnify as the arguments of peanut_stg_plan; lmb [E][4]; start_exact [E][2];
+ * result_out [E] (host); trav_out / goal_out / dist_out optional arrays of E optional device taps of each episode's LAST solve.
+ * The stream the work is enqueued on travels in the descriptor.  Synchronises (once per wave, and inside every solve).
+ * PEANUT_EINVAL with nothing enqueued and no result or tap written: a wrong size, E outside 1..PEANUT_STG_MAX_BATCH, a null array
+ * or a null entry (the tap arrays and their entries excepted), the same handle twice, handles that differ in m, full_w, full_h,
+ * col_rad, step_size or the solver options, and every per-episode condition peanut_stg_plan refuses.  A solve that fails part-way
+ * lets the stream run out before the error returns. */
+#define PEANUT_STG_MAX_BATCH PEANUT_GOAL_MAX_BATCH
+typedef struct {
+  uint64_t size;                          /* sizeof(peanut_stg_batch_t) */
+  int32_t E, reserved;
+  peanut_stg_t* const* h;
+  const float* const* obstacle;
+  const long long* row_stride;
+  const uint8_t* const* goal_map;
+  const uint8_t* const* collision;
+  const uint8_t* const* visited;
+  const int* lmb;                         /* [E][4] */
+  const double* start_exact;              /* [E][2] */
+  const int* found_goal;
+  const int* radius_found;
+  const double* magnify_when_hard;
+  const int* max_magnify;
+  peanut_stg_result_t* result_out;        /* [E], host */
+  uint8_t* const* trav_out;               /* optional */
+  uint8_t* const* goal_out;               /* optional */
+  double* const* dist_out;                /* optional */
+  void* stream;
+} peanut_stg_batch_t;
+int peanut_stg_plan_batch(const peanut_stg_batch_t* batch);
+/* Test hook: the synchronising waves of the last plan this handle took part in (peanut_stg_plan: its n_solves; a batch: the
+ * largest n_solves among its episodes). */
+int peanut_stg_waves(peanut_stg_t* h);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: collation of the predicted maps for logging.  One process per GPU, maps /

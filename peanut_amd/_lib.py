@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 19    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 20    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -72,6 +72,17 @@ class StgResultC(C.Structure):
     """peanut_stg_result_t: what peanut_stg_plan returns on the host."""
     _fields_ = [("stg_x", C.c_double), ("stg_y", C.c_double), ("distance", C.c_double), ("stop", C.c_int32), ("replan", C.c_int32),
                 ("retried", C.c_int32), ("n_magnify", C.c_int32), ("n_solves", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StgBatchC(C.Structure):
+    """peanut_stg_batch_t: the descriptor of peanut_stg_plan_batch (host arrays of E entries; ``size`` first)."""
+    _fields_ = [("size", C.c_uint64), ("E", C.c_int32), ("reserved", C.c_int32),
+                ("h", C.POINTER(C.c_void_p)), ("obstacle", C.POINTER(C.c_void_p)), ("row_stride", C.POINTER(C.c_longlong)),
+                ("goal_map", C.POINTER(C.c_void_p)), ("collision", C.POINTER(C.c_void_p)), ("visited", C.POINTER(C.c_void_p)),
+                ("lmb", C.POINTER(C.c_int)), ("start_exact", C.POINTER(C.c_double)), ("found_goal", C.POINTER(C.c_int)),
+                ("radius_found", C.POINTER(C.c_int)), ("magnify_when_hard", C.POINTER(C.c_double)), ("max_magnify", C.POINTER(C.c_int)),
+                ("result_out", C.POINTER(StgResultC)), ("trav_out", C.POINTER(C.c_void_p)), ("goal_out", C.POINTER(C.c_void_p)),
+                ("dist_out", C.POINTER(C.c_void_p)), ("stream", C.c_void_p)]
 
 
 class TensorC(C.Structure):
@@ -169,6 +180,8 @@ SIGNATURES = {
     "peanut_stg_destroy": (None, [_P]),
     "peanut_stg_plan": (C.c_int, [_P, _P, C.c_longlong, _P, _P, _P, C.POINTER(C.c_int * 4), C.POINTER(C.c_double * 2), C.c_int, C.c_int,
                                   C.c_double, C.c_int, C.POINTER(StgResultC), _P, _P, _P, _P]),
+    "peanut_stg_plan_batch": (C.c_int, [C.POINTER(StgBatchC)]),
+    "peanut_stg_waves": (C.c_int, [_P]),
     "peanut_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_destroy": (None, [_P]),

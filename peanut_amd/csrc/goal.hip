@@ -58,6 +58,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "goal_internal.h"
 #include "net_common.h"
 
 #pragma clang fp contract(off)
@@ -88,7 +89,13 @@ struct FieldBatchArgs {
   unsigned char* state[GB];
   unsigned char* active[GB];      // four flag arrays of tiles_x * tiles_y bytes each (field_preamble)
   int seed_r[GB], seed_c[GB];
-  unsigned int done;              // bit e: episode e takes no part in this launch (its passes ended, or its stage has settled)
+  unsigned int done;              // bit e: episode e takes no part in this launch (its passes ended, its stage has settled, or the caller left it out)
+};
+// the batched field on given masks (fmm_distance_masks_batch): what peanut_fmm_distance(g, trav, goal_mask, -1, -1, 1, out) takes, per episode
+struct MaskBatchArgs {
+  const unsigned char *trav[GB], *seed[GB];
+  unsigned long long* max_bits[GB];      // slot 0 of the episode's own maxbits, as in the single call
+  double* out[GB];
 };
 
 // ---- traversible map: ~dilate(rint(obstacle), disk(rad)), collision -> 0, visited -> 1  (agent_state.py:382-386) ----
@@ -208,6 +215,14 @@ __global__ __launch_bounds__(256) void fmm_init_batch_kernel(FieldBatchArgs a, T
   const int e = blockIdx.y;
   unsigned char* act = a.active[e];
   fmm_init_body(t.trav[e], nullptr, a.seed_r[e], a.seed_c[e], H, W, a.state[e], a.dist[e], act + 3 * (size_t)nt, act, tiles_x);
+}
+// the same with a seed MASK per episode (no seed cell) on maps the caller gives; also zeroes the slot the fill's maximum is formed in
+__global__ __launch_bounds__(256) void fmm_init_mask_batch_kernel(FieldBatchArgs a, MaskBatchArgs m, int H, int W, int tiles_x, int nt) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *m.max_bits[e] = 0ull;
+  unsigned char* act = a.active[e];
+  fmm_init_body(m.trav[e], m.seed[e], -1, -1, H, W, a.state[e], a.dist[e], act + 3 * (size_t)nt, act, tiles_x);
 }
 
 // one axis of distanceMarcher::updatePointOrderTwo.  m1/m2 = the values one and two steps towards smaller indices,
@@ -657,7 +672,7 @@ __global__ __launch_bounds__(256) void fmm_pass_batch_kernel(FieldBatchArgs a, i
 }
 
 // max over the reached cells (for `ma.filled(dd, np.max(dd) + 1)`); bits of a non-negative double order like an integer
-__global__ __launch_bounds__(256) void fmm_max_kernel(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
+__device__ __forceinline__ void fmm_max_body(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
   double m = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const double v = dist[i];
@@ -666,12 +681,29 @@ __global__ __launch_bounds__(256) void fmm_max_kernel(const double* __restrict__
   for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
   if ((threadIdx.x & 63) == 0) atomicMax(max_bits, (unsigned long long)__double_as_longlong(m));
 }
-__global__ __launch_bounds__(256) void fmm_fill_kernel(const double* __restrict__ dist, int n, const unsigned long long* __restrict__ max_bits,
-                                                       double* __restrict__ out) {
+__global__ __launch_bounds__(256) void fmm_max_kernel(const double* __restrict__ dist, int n, unsigned long long* __restrict__ max_bits) {
+  fmm_max_body(dist, n, max_bits);
+}
+__global__ __launch_bounds__(256) void fmm_max_batch_kernel(FieldBatchArgs a, MaskBatchArgs m, int n) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  fmm_max_body(a.dist[e], n, m.max_bits[e]);
+}
+__device__ __forceinline__ void fmm_fill_body(const double* __restrict__ dist, int n, const unsigned long long* __restrict__ max_bits,
+                                              double* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double v = dist[i];
   out[i] = v < INFINITY ? v : __longlong_as_double((long long)*max_bits) + 1.0;
+}
+__global__ __launch_bounds__(256) void fmm_fill_kernel(const double* __restrict__ dist, int n, const unsigned long long* __restrict__ max_bits,
+                                                       double* __restrict__ out) {
+  fmm_fill_body(dist, n, max_bits, out);
+}
+__global__ __launch_bounds__(256) void fmm_fill_batch_kernel(FieldBatchArgs a, MaskBatchArgs m, int n) {
+  const int e = blockIdx.y;
+  if ((a.done >> e) & 1u) return;
+  fmm_fill_body(a.dist[e], n, m.max_bits[e], m.out[e]);
 }
 
 // max over ALL cells, +inf included (for `dd[dd == np.max(dd)] = np.inf` after the fill, :392-393): +inf when some cell is masked or
@@ -1262,20 +1294,36 @@ int run_stage_batch(GoalBatch* B, int E, peanut_goal_t* const* g, const FieldBat
   return fail(PEANUT_EHIP, "fmm: a relaxation stage of the batch did not settle within its round budget");
 }
 
-// begun_batch > 0: the preamble and that many stage-A rounds are already on `s` (begun_cur = the flag rotation after them)
+// state, distances, seed tiles of the episodes not in fa.done, from given traversible maps and seed masks: two launches
+int field_preamble_masks_batch(int E, peanut_goal* g0, const FieldBatchArgs& fa, const MaskBatchArgs& ma, hipStream_t s) {
+  const int H = g0->H, W = g0->W, n = H * W, nt = g0->tiles_x * g0->tiles_y;
+  hipLaunchKernelGGL(fmm_flags_clear_batch_kernel, dim3((4 * nt + 255) / 256, E), dim3(256), 0, s, fa, 4 * nt);
+  hipLaunchKernelGGL(fmm_init_mask_batch_kernel, dim3((n + 255) / 256, E), dim3(256), 0, s, fa, ma, H, W, g0->tiles_x, nt);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("fmm_distance_masks_batch: ") + hipGetErrorString(e));
+}
+
+// begun_batch > 0: the preamble and that many stage-A rounds are already on `s` (begun_cur = the flag rotation after them).
+// skip: episodes (bits) that take no part at all -- their slots stay where they are, nothing of theirs is read or written but the
+// flag arrays, which are scratch; masks: the preamble is the one on given masks (ta is not looked at)
 int solve_field_batch(GoalBatch* B, int E, peanut_goal_t* const* g, const FieldBatchArgs& fa, const TravBatchArgs& ta, hipStream_t s,
-                      int begun_batch, int begun_cur) {
+                      int begun_batch, int begun_cur, unsigned int skip = 0u, const MaskBatchArgs* masks = nullptr) {
   const int n = g[0]->H * g[0]->W, nt = g[0]->tiles_x * g[0]->tiles_y;
   int cur = 0, rounds = 0;
   unsigned long long changed[GB];
-  unsigned int done = E >= 32 ? 0u : ~((1u << E) - 1u);
+  unsigned int done = (E >= 32 ? 0u : ~((1u << E) - 1u)) | skip;
   if (begun_batch > 0) {
     cur = begun_cur;
+  } else if (masks) {
+    FieldBatchArgs ia = fa;
+    ia.done = done;
+    if (int rc = field_preamble_masks_batch(E, g[0], ia, *masks, s)) return rc;
   } else if (int rc = field_preamble_batch(E, g[0], fa, ta, s)) {
     return rc;
   }
   if (int rc = run_stage_batch<false>(B, E, g, fa, 0, done, &cur, &rounds, changed, s, begun_batch)) return rc;
-  for (int e = 0; e < E; ++e) { g[e]->last_passes = 0; g[e]->last_converged = false; }
+  for (int e = 0; e < E; ++e)
+    if (!((skip >> e) & 1u)) { g[e]->last_passes = 0; g[e]->last_converged = false; }
   const int max_passes = (int)std::min<long long>(std::max<long long>(opt(OPT_FMM_MAX_PASSES), 2), 64);
   for (int pass = 0; pass < max_passes && done != 0xffffffffu; ++pass) {
     FieldBatchArgs pa = fa;
@@ -1289,13 +1337,72 @@ int solve_field_batch(GoalBatch* B, int E, peanut_goal_t* const* g, const FieldB
       if (pass > 0 && changed[e] == 0) { g[e]->last_converged = true; done |= 1u << e; }
     }
   }
-  for (int e = 0; e < E; ++e) g[e]->last_rounds = rounds;
+  for (int e = 0; e < E; ++e)
+    if (!((skip >> e) & 1u)) g[e]->last_rounds = rounds;
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return fail(PEANUT_EHIP, std::string("fmm: ") + hipGetErrorString(err));
   return 0;
 }
 
 }  // namespace
+
+// ---- the batched field on given masks (goal_internal.h): peanut_fmm_distance(g, trav, goal_mask, -1, -1, 1, out) for E handles ----
+namespace peanut {
+
+const char* fmm_masks_batch_bad(int E, peanut_goal_t* const* g) {
+  if (E < 1 || E > GB) return "E must be 1..PEANUT_GOAL_MAX_BATCH";
+  if (!g) return "null argument";
+  static const OptionId same[] = {OPT_FMM_BLOCKED, OPT_FMM_LOCAL32, OPT_FMM_INNER, OPT_FMM_MAX_PASSES};
+  for (int e = 0; e < E; ++e) {
+    if (!g[e]) return "null solver handle";
+    for (int f = 0; f < e; ++f)
+      if (g[f] == g[e]) return "the same solver handle appears twice";
+    if (g[e]->H != g[0]->H || g[e]->W != g[0]->W) return "the solver handles differ in map size";
+    for (OptionId id : same)
+      if (g[e]->opts.v[id] != g[0]->opts.v[id]) return "the solver handles differ in their solver options";
+  }
+  return nullptr;
+}
+
+int fmm_masks_batch_prepare(int E, peanut_goal_t* const* g) {
+  if (const char* why = fmm_masks_batch_bad(E, g)) return fail(PEANUT_EINVAL, std::string("fmm_distance_masks_batch: ") + why);
+  if (int rc = ensure_batch(g[0])) return rc;
+  drain_all(E, g);
+  return 0;
+}
+
+int fmm_distance_masks_batch(int E, peanut_goal_t* const* g, const unsigned char* const* trav, const unsigned char* const* seed_mask,
+                             double* const* out, unsigned int skip, hipStream_t s) {
+  if (const char* why = fmm_masks_batch_bad(E, g)) return fail(PEANUT_EINVAL, std::string("fmm_distance_masks_batch: ") + why);
+  if (!trav || !seed_mask || !out) return fail(PEANUT_EINVAL, "fmm_distance_masks_batch: null argument");
+  const unsigned int all = (1u << E) - 1u;
+  skip &= all;
+  if (skip == all) return 0;
+  for (int e = 0; e < E; ++e)
+    if (!((skip >> e) & 1u) && (!trav[e] || !seed_mask[e] || !out[e])) return fail(PEANUT_EINVAL, "fmm_distance_masks_batch: null map");
+  peanut::OptionScope option_scope(&g[0]->opts);
+  if (int rc = ensure_batch(g[0])) return rc;      // (made by fmm_masks_batch_prepare; a guard)
+  GoalBatch* B = g[0]->batch.get();
+  FieldBatchArgs fa{};
+  TravBatchArgs ta{};
+  MaskBatchArgs ma{};
+  for (int e = 0; e < E; ++e) {
+    fa.dist[e] = (double*)g[e]->dist.p; fa.ord[e] = (double*)g[e]->order.p;
+    fa.state[e] = (unsigned char*)g[e]->state.p; fa.active[e] = (unsigned char*)g[e]->active.p;
+    fa.seed_r[e] = -1; fa.seed_c[e] = -1;
+    ma.trav[e] = trav[e]; ma.seed[e] = seed_mask[e]; ma.out[e] = out[e];
+    ma.max_bits[e] = (unsigned long long*)g[e]->maxbits.p;
+  }
+  if (int rc = solve_field_batch(B, E, g, fa, ta, s, 0, 0, skip, &ma)) return rc;
+  const int n = g[0]->H * g[0]->W;
+  fa.done = ~all | skip;
+  hipLaunchKernelGGL(fmm_max_batch_kernel, dim3(256, E), dim3(256), 0, s, fa, ma, n);
+  hipLaunchKernelGGL(fmm_fill_batch_kernel, dim3((n + 255) / 256, E), dim3(256), 0, s, fa, ma, n);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("fmm_distance_masks_batch: ") + hipGetErrorString(e));
+}
+
+}  // namespace peanut
 
 extern "C" {
 

@@ -16,7 +16,13 @@
 //     kernel-argument block.
 //
 // peanut_stg_plan is _get_stg's control flow over them; its loop conditions are host decisions on the 24-byte struct the window kernel
-// wrote.  All of it is binary morphology, comparisons and a handful of double operations without contraction: everything but the
+// wrote.  peanut_stg_plan_batch is the same for up to PEANUT_STG_MAX_BATCH episodes of a lock-step group, each with its own handle
+// and its own state machine (StgEpisode), run in WAVES: the masks of every unfinished episode's next solve (the traversible maps of
+// a wave in one launch, the grown goals in one), one batched solve on those masks (fmm_distance_masks_batch of goal.hip, declared in
+// goal_internal.h), one window launch over the episodes, one read-back of the [E] window structs and one synchronisation; the
+// host then advances every episode.  The waves of a call are the solves of its LONGEST chain, not of all chains in a row.  The
+// window masks of 16 episodes (31 KB) do not fit the kernel-argument block: they go up once per call through a pinned table, and
+// the window body reads them through a pointer in both forms.  All of it is binary morphology, comparisons and a handful of double operations without contraction: everything but the
 // solver's field is held to the reference bit for bit.
 #include <math.h>
 
@@ -24,6 +30,7 @@
 #include <memory>
 #include <string>
 
+#include "goal_internal.h"
 #include "net_common.h"
 
 #pragma clang fp contract(off)
@@ -79,8 +86,13 @@ struct StgTravP {
   int blk_r0, blk_r1, blk_c0, blk_c1;         // the start block as half-open ranges (:417-418)
 };
 
+// Every kernel below exists twice, as in goal.hip: for one episode, and for up to SB episodes of a lock-step group in one launch
+// (peanut_stg_plan_batch: the episode is a grid dimension, the per-episode arguments travel by value in SB slots).  Both are thin
+// wrappers around ONE __device__ body.
+constexpr int SB = PEANUT_STG_MAX_BATCH;
+
 // grid (ceil((m + 2) / 32), ceil((m + 2) / 8)) over the PADDED output; the grid's cell is the padded one minus one
-__global__ __launch_bounds__(256) void stg_trav_kernel(const StgTravP p) {
+__device__ __forceinline__ void stg_trav_body(const StgTravP& p) {
   const int m = p.m, n = m + 2;
   // the bordered grid (:377-390): rint(obstacle) != 0, or a border rule
   auto grid_bit = [&](int r, int c) -> bool {
@@ -110,10 +122,14 @@ __global__ __launch_bounds__(256) void stg_trav_kernel(const StgTravP p) {
   }
   p.out[(size_t)pr * n + pc] = t;
 }
+__global__ __launch_bounds__(256) void stg_trav_kernel(const StgTravP p) { stg_trav_body(p); }
+struct StgTravBatch { StgTravP p[SB]; };
+// grid (.., .., slots): the maps one wave of the batch needs
+__global__ __launch_bounds__(256) void stg_trav_batch_kernel(const StgTravBatch a) { stg_trav_body(a.p[blockIdx.z]); }
 
 // grid as above; in: [m, m] (padded = 0) or [(m + 2), (m + 2)]
-__global__ __launch_bounds__(256) void stg_goal_kernel(const unsigned char* __restrict__ in, int padded, int m, int rad,
-                                                       unsigned char* __restrict__ out) {
+__device__ __forceinline__ void stg_goal_body(const unsigned char* __restrict__ in, int padded, int m, int rad,
+                                              unsigned char* __restrict__ out) {
   const int n = m + 2;
   auto bit = [&](int pr, int pc) -> bool {
     if (padded) return (unsigned)pr < (unsigned)n && (unsigned)pc < (unsigned)n && in[(size_t)pr * n + pc] != 0;
@@ -125,12 +141,27 @@ __global__ __launch_bounds__(256) void stg_goal_kernel(const unsigned char* __re
   const int pr = pr0 + (threadIdx.x >> 5), pc = pc0 + (threadIdx.x & 31);
   if (pr < n && pc < n) out[(size_t)pr * n + pc] = hit ? 1 : 0;
 }
+__global__ __launch_bounds__(256) void stg_goal_kernel(const unsigned char* __restrict__ in, int padded, int m, int rad,
+                                                       unsigned char* __restrict__ out) {
+  stg_goal_body(in, padded, m, rad, out);
+}
+struct StgGoalBatch {
+  const unsigned char* in[SB];
+  unsigned char* out[SB];
+  int padded[SB], rad[SB];
+};
+__global__ __launch_bounds__(256) void stg_goal_batch_kernel(const StgGoalBatch a, int m) {
+  const int j = blockIdx.z;
+  stg_goal_body(a.in[j], a.padded[j], m, a.rad[j], a.out[j]);
+}
 
 struct StgMasks { double mask[STG_MAX_CELLS], dist[STG_MAX_CELLS]; };      // [(2 du + 1)^2] each, packed
 
-// get_short_term_goal (fmm_planner.py:86-116): one workgroup of 128 threads, a thread per window cell
-__global__ __launch_bounds__(128) void stg_window_kernel(const double* __restrict__ field, int n, int ir, int ic, int du,
-                                                         const StgMasks M, peanut_stg_window_t* __restrict__ out) {
+// get_short_term_goal (fmm_planner.py:86-116): one workgroup of 128 threads, a thread per window cell.  The masks are read through
+// a pointer: into the kernel-argument block in the single form, into the batch's device table in the other.
+__device__ __forceinline__ void stg_window_body(const double* __restrict__ field, int n, int ir, int ic, int du, const StgMasks* Mp,
+                                                peanut_stg_window_t* __restrict__ out) {
+  const StgMasks& M = *Mp;
   __shared__ double sub[STG_MAX_CELLS];
   __shared__ double centre;
   const int side = 2 * du + 1, cells = side * side, t = threadIdx.x;
@@ -166,6 +197,22 @@ __global__ __launch_bounds__(128) void stg_window_kernel(const double* __restric
     out->replan = bv > -0.0001 ? 1 : 0;
   }
 }
+__global__ __launch_bounds__(128) void stg_window_kernel(const double* __restrict__ field, int n, int ir, int ic, int du,
+                                                         const StgMasks M, peanut_stg_window_t* __restrict__ out) {
+  stg_window_body(field, n, ir, ic, du, &M, out);
+}
+struct StgWindowBatch {
+  const double* field[SB];
+  int ir[SB], ic[SB];
+  unsigned int skip;              // bit e: episode e has no solve in this wave
+};
+// grid (E): masks [E] and out [E] are the batch's device tables, indexed by the episode
+__global__ __launch_bounds__(128) void stg_window_batch_kernel(const StgWindowBatch a, int n, int du, const StgMasks* __restrict__ masks,
+                                                               peanut_stg_window_t* __restrict__ out) {
+  const int e = blockIdx.x;
+  if ((a.skip >> e) & 1u) return;
+  stg_window_body(a.field[e], n, a.ir[e], a.ic[e], du, masks + e, out + e);
+}
 
 // Python's a[i - 1:i + 2] on an axis of m cells, i >= 0, as a half-open range
 void start_block(int i, int m, int* lo, int* hi) {
@@ -175,9 +222,8 @@ void start_block(int i, int m, int* lo, int* hi) {
   *hi = b > m ? m : b;
 }
 
-int trav_launch(const float* obstacle, long long row_stride, int m, int full_w, int full_h, const int lmb[4], int col_rad, int erode,
-                const unsigned char* collision, const unsigned char* visited, int start_r, int start_c, unsigned char* trav_out,
-                hipStream_t s) {
+StgTravP trav_params(const float* obstacle, long long row_stride, int m, int full_w, int full_h, const int lmb[4], int col_rad, int erode,
+                     const unsigned char* collision, const unsigned char* visited, int start_r, int start_c, unsigned char* trav_out) {
   StgTravP p{};
   p.obst = obstacle; p.col = collision; p.vis = visited; p.out = trav_out; p.rs = row_stride;
   p.m = m; p.full_h = full_h; p.gx1 = lmb[0]; p.gy1 = lmb[2];
@@ -186,6 +232,13 @@ int trav_launch(const float* obstacle, long long row_stride, int m, int full_w, 
   p.rad = col_rad; p.erode = erode ? 1 : 0;
   start_block(start_r, m, &p.blk_r0, &p.blk_r1);
   start_block(start_c, m, &p.blk_c0, &p.blk_c1);
+  return p;
+}
+
+int trav_launch(const float* obstacle, long long row_stride, int m, int full_w, int full_h, const int lmb[4], int col_rad, int erode,
+                const unsigned char* collision, const unsigned char* visited, int start_r, int start_c, unsigned char* trav_out,
+                hipStream_t s) {
+  const StgTravP p = trav_params(obstacle, row_stride, m, full_w, full_h, lmb, col_rad, erode, collision, visited, start_r, start_c, trav_out);
   const int n = m + 2;
   hipLaunchKernelGGL(stg_trav_kernel, dim3((n + 31) / 32, (n + 7) / 8), dim3(256), 0, s, p);
   return 0;
@@ -247,8 +300,21 @@ int launched(const char* who) {
 
 using namespace peanut;
 
+// What a batched plan needs beyond the episodes' own handles; owned by the FIRST handle of the batch, made on first use.
+struct StgBatch {
+  DevBuf masks, results;                            // [SB] StgMasks, [SB] peanut_stg_window_t
+  StgMasks* host_masks = nullptr;                   // pinned mirrors
+  peanut_stg_window_t* host_results = nullptr;
+  ~StgBatch() {
+    if (host_masks) (void)hipHostFree(host_masks);
+    if (host_results) (void)hipHostFree(host_results);
+  }
+};
+
 struct peanut_stg {
   int m = 0, full_w = 0, full_h = 0, col_rad = 0, step_size = 0;
+  int last_waves = 0;                               // synchronising waves of the last plan this handle took part in (peanut_stg_waves)
+  std::unique_ptr<StgBatch> batch;                  // this handle leads batches (it is their first): their shared tables
   peanut_goal_t* solver = nullptr;                  // (m + 2) x (m + 2)
   DevBuf trav, goal[2], field, result;
   peanut_stg_window_t* host_result = nullptr;       // pinned
@@ -381,7 +447,182 @@ int peanut_stg_plan(peanut_stg_t* h, const float* obstacle, long long row_stride
   result_out->n_magnify = n_magnify;
   result_out->n_solves = n_solves;
   result_out->reserved = 0;
+  h->last_waves = n_solves;
   return launched("peanut_stg_plan");
+}
+
+int peanut_stg_waves(peanut_stg_t* h) { return h ? h->last_waves : PEANUT_EINVAL; }
+
+namespace {
+
+int ensure_stg_batch(peanut_stg* lead) {
+  if (lead->batch) return 0;
+  auto B = std::make_unique<StgBatch>();
+  if (int rc = B->masks.ensure((size_t)SB * sizeof(StgMasks))) return rc;
+  if (int rc = B->results.ensure((size_t)SB * sizeof(peanut_stg_window_t))) return rc;
+  PEANUT_HIP_CHECK(hipHostMalloc((void**)&B->host_masks, (size_t)SB * sizeof(StgMasks), hipHostMallocDefault));
+  PEANUT_HIP_CHECK(hipHostMalloc((void**)&B->host_results, (size_t)SB * sizeof(peanut_stg_window_t), hipHostMallocDefault));
+  lead->batch = std::move(B);
+  return 0;
+}
+
+// one episode of the batch: _get_stg's control flow (peanut_stg_plan) as a state machine that is advanced once per wave
+struct StgEpisode {
+  enum Next { FIRST, RETRY, MAGNIFY, DONE } next = FIRST;      // the solve this episode takes in the coming wave
+  int cur = 0, retried = 0, n_magnify = 0, n_solves = 0, step = 0, in_magnify = 0;
+  peanut_stg_window_t w{};
+  // after a solve whose window result is w: which solve follows (the conditions of peanut_stg_plan, in its order)
+  void advance(int found_goal, double magnify_when_hard, int max_magnify) {
+    ++n_solves;
+    if (next == FIRST && w.replan) { next = RETRY; return; }               // failed to plan a path (:443-469)
+    if (!in_magnify) {
+      if (!(found_goal == 1 && w.distance > magnify_when_hard)) { next = DONE; return; }
+      in_magnify = 1;                                                      // make the goal larger (:473-489)
+    }
+    if (!(w.distance > 100.0)) { next = DONE; return; }
+    ++step;
+    next = step > max_magnify ? DONE : MAGNIFY;
+  }
+};
+
+}  // namespace
+
+int peanut_stg_plan_batch(const peanut_stg_batch_t* b) {
+  const char* who = "peanut_stg_plan_batch: ";
+  if (!b || b->size != sizeof(peanut_stg_batch_t)) return fail(PEANUT_EINVAL, std::string(who) + "size is not sizeof(peanut_stg_batch_t)");
+  const int E = b->E;
+  if (E < 1 || E > SB) return fail(PEANUT_EINVAL, std::string(who) + "E must be 1..PEANUT_STG_MAX_BATCH");
+  if (!b->h || !b->obstacle || !b->row_stride || !b->goal_map || !b->collision || !b->visited || !b->lmb || !b->start_exact ||
+      !b->found_goal || !b->radius_found || !b->magnify_when_hard || !b->max_magnify || !b->result_out)
+    return fail(PEANUT_EINVAL, std::string(who) + "null array");
+  peanut_stg* const* h = b->h;
+  peanut_goal_t* solver[SB];
+  int radius[SB], sr[SB], sc[SB];
+  double state_r[SB], state_c[SB];
+  for (int e = 0; e < E; ++e) {
+    if (!h[e] || !b->obstacle[e] || !b->goal_map[e] || !b->collision[e] || !b->visited[e]) return fail(PEANUT_EINVAL, std::string(who) + "null entry");
+    for (int f = 0; f < e; ++f)
+      if (h[f] == h[e]) return fail(PEANUT_EINVAL, std::string(who) + "the same handle appears twice");
+    if (h[e]->m != h[0]->m || h[e]->full_w != h[0]->full_w || h[e]->full_h != h[0]->full_h || h[e]->col_rad != h[0]->col_rad ||
+        h[e]->step_size != h[0]->step_size)
+      return fail(PEANUT_EINVAL, std::string(who) + "the handles differ in m, full_w, full_h, col_rad or step_size");
+    solver[e] = h[e]->solver;
+  }
+  const int m = h[0]->m, n = m + 2, step_size = h[0]->step_size;
+  if (m < 2 * step_size + 1) return fail(PEANUT_EINVAL, std::string(who) + "m < 2 step_size + 1");
+  for (int e = 0; e < E; ++e) {      // every per-episode condition peanut_stg_plan refuses
+    const double* se = b->start_exact + 2 * e;
+    if (!(se[0] >= 0.0 && se[0] < (double)m && se[1] >= 0.0 && se[1] < (double)m)) return fail(PEANUT_EINVAL, std::string(who) + "start_exact outside [0, m)");
+    radius[e] = b->found_goal[e] == 1 ? b->radius_found[e] : 2;      // (:425-430)
+    if (radius[e] < 0 || radius[e] > STG_MAX_RAD) return fail(PEANUT_EINVAL, std::string(who) + "goal radius must be 0..PEANUT_STG_MAX_RAD");
+    sr[e] = (int)se[0]; sc[e] = (int)se[1];
+    if (const char* why = trav_args_bad(b->obstacle[e], b->row_stride[e], m, h[e]->full_w, h[e]->full_h, b->lmb + 4 * e, h[e]->col_rad, sr[e], sc[e]))
+      return fail(PEANUT_EINVAL, std::string(who) + why);
+    state_r[e] = se[0] + 1.0; state_c[e] = se[1] + 1.0;              // (:438)
+    if (const char* why = window_args_bad((const double*)h[e]->field.p, n, state_r[e], state_c[e], step_size, h[e]->result.p))
+      return fail(PEANUT_EINVAL, std::string(who) + why);
+  }
+  if (const char* why = fmm_masks_batch_bad(E, solver)) return fail(PEANUT_EINVAL, std::string(who) + why);
+  // nothing below refuses; what the call needs beyond the handles exists after these two (first use of this lead only)
+  if (int rc = ensure_stg_batch(h[0])) return rc;
+  if (int rc = fmm_masks_batch_prepare(E, solver)) return rc;
+  hipStream_t s = (hipStream_t)b->stream;
+  StgBatch* B = h[0]->batch.get();
+  // a failure part-way: the stream runs out before the error returns (the tables and the handles' maps are free again)
+  auto out = [&](int rc) -> int {
+    if (rc) (void)hipStreamSynchronize(s);
+    return rc;
+  };
+  // start_exact is fixed for the call: the window masks of all episodes go up once
+  StgWindowBatch wa{};
+  const unsigned char* trav[SB];
+  const unsigned char* seed[SB];
+  double* field[SB];
+  for (int e = 0; e < E; ++e) {
+    wa.ir[e] = (int)state_r[e]; wa.ic[e] = (int)state_c[e];          // int(x): towards zero; the state is >= 0
+    wa.field[e] = (const double*)h[e]->field.p;
+    stg_masks(state_r[e] - (double)wa.ir[e], state_c[e] - (double)wa.ic[e], step_size, B->host_masks[e].mask, B->host_masks[e].dist);
+    trav[e] = (const unsigned char*)h[e]->trav.p;
+    field[e] = (double*)h[e]->field.p;
+  }
+  if (hipMemcpyAsync(B->masks.p, B->host_masks, (size_t)E * sizeof(StgMasks), hipMemcpyHostToDevice, s) != hipSuccess)
+    return out(fail(PEANUT_EHIP, std::string(who) + "the upload of the window masks failed"));
+  StgEpisode ep[SB];
+  const unsigned int all = (1u << E) - 1u;
+  const dim3 mgrid2((n + 31) / 32, (n + 7) / 8);
+  int waves = 0;
+  for (;;) {
+    // every unfinished episode prepares the masks of its next solve: the traversible maps of the wave in one launch, the goals in one
+    StgTravBatch ta{};
+    StgGoalBatch ga{};
+    int nt = 0, ng = 0;
+    unsigned int skip = 0u;
+    for (int e = 0; e < E; ++e) {
+      StgEpisode& x = ep[e];
+      if (x.next == StgEpisode::DONE) { skip |= 1u << e; continue; }
+      if (x.next == StgEpisode::FIRST || x.next == StgEpisode::RETRY) {
+        if (x.next == StgEpisode::RETRY) x.retried = 1;
+        ta.p[nt++] = trav_params(b->obstacle[e], b->row_stride[e], m, h[e]->full_w, h[e]->full_h, b->lmb + 4 * e, h[e]->col_rad,
+                                 x.next == StgEpisode::RETRY ? 1 : 0, b->collision[e], b->visited[e], sr[e], sc[e], (unsigned char*)h[e]->trav.p);
+      }
+      if (x.next == StgEpisode::FIRST) {
+        ga.in[ng] = b->goal_map[e]; ga.padded[ng] = 0; ga.rad[ng] = radius[e]; ga.out[ng] = (unsigned char*)h[e]->goal[x.cur].p;
+        ++ng;
+      } else if (x.next == StgEpisode::MAGNIFY) {
+        ga.in[ng] = (const unsigned char*)h[e]->goal[x.cur].p; ga.padded[ng] = 1; ga.rad[ng] = 2; ga.out[ng] = (unsigned char*)h[e]->goal[x.cur ^ 1].p;
+        ++ng;
+        x.cur ^= 1;
+        ++x.n_magnify;
+      }
+      seed[e] = (const unsigned char*)h[e]->goal[x.cur].p;
+    }
+    if (skip == all) break;
+    if (nt) hipLaunchKernelGGL(stg_trav_batch_kernel, dim3(mgrid2.x, mgrid2.y, nt), dim3(256), 0, s, ta);
+    if (ng) hipLaunchKernelGGL(stg_goal_batch_kernel, dim3(mgrid2.x, mgrid2.y, ng), dim3(256), 0, s, ga, m);
+    // planner.set_multi_goal(goal); planner.get_short_term_goal(state), for the episodes of this wave
+    if (int rc = fmm_distance_masks_batch(E, solver, trav, seed, field, skip, s)) return out(rc);
+    wa.skip = skip;
+    hipLaunchKernelGGL(stg_window_batch_kernel, dim3(E), dim3(128), 0, s, wa, n, step_size, (const StgMasks*)B->masks.p,
+                       (peanut_stg_window_t*)B->results.p);
+    if (hipMemcpyAsync(B->host_results, B->results.p, (size_t)E * sizeof(peanut_stg_window_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return out(fail(PEANUT_EHIP, std::string(who) + "the read-back of a wave failed"));
+    ++waves;
+    for (int e = 0; e < E; ++e) {
+      if ((skip >> e) & 1u) continue;
+      ep[e].w = B->host_results[e];
+      ep[e].advance(b->found_goal[e], b->magnify_when_hard[e], b->max_magnify[e]);
+    }
+  }
+  const size_t n2 = (size_t)n * n;
+  bool taps = false;
+  for (int e = 0; e < E; ++e) {
+    uint8_t* t = b->trav_out ? b->trav_out[e] : nullptr;
+    uint8_t* g = b->goal_out ? b->goal_out[e] : nullptr;
+    double* d = b->dist_out ? b->dist_out[e] : nullptr;
+    hipError_t err = hipSuccess;
+    if (t) err = hipMemcpyAsync(t, h[e]->trav.p, n2, hipMemcpyDeviceToDevice, s);
+    if (g && err == hipSuccess) err = hipMemcpyAsync(g, h[e]->goal[ep[e].cur].p, n2, hipMemcpyDeviceToDevice, s);
+    if (d && err == hipSuccess) err = hipMemcpyAsync(d, h[e]->field.p, n2 * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (err != hipSuccess) return out(fail(PEANUT_EHIP, std::string(who) + "a tap copy failed"));
+    taps = taps || t || g || d;
+  }
+  if (taps) PEANUT_HIP_CHECK(hipStreamSynchronize(s));
+  for (int e = 0; e < E; ++e) {
+    const StgEpisode& x = ep[e];
+    peanut_stg_result_t* r = b->result_out + e;
+    r->stg_x = (double)x.w.stg_r - 1.0;        // stg_x + x1 - 1 (:491)
+    r->stg_y = (double)x.w.stg_c - 1.0;
+    r->distance = x.w.distance;
+    r->stop = x.w.stop;
+    r->replan = x.w.replan;
+    r->retried = x.retried;
+    r->n_magnify = x.n_magnify;
+    r->n_solves = x.n_solves;
+    r->reserved = 0;
+    h[e]->last_waves = waves;
+  }
+  return launched("peanut_stg_plan_batch");
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@ from . import _lib
 
 MAX_RAD = 16      # PEANUT_STG_MAX_RAD
 MAX_STEP = 5      # PEANUT_STG_MAX_STEP
+MAX_BATCH = 16    # PEANUT_STG_MAX_BATCH
 
 
 def stg_masks(sx: float, sy: float, step_size: int = 5):
@@ -108,10 +109,12 @@ class ShortTermGoal:
                 pass
             self._h = C.c_void_p()
 
-    def get_stg(self, obstacle, goal_map, collision_map, visited_vis, lmb, start_exact, found_goal, goal_name, taps: bool = False):
-        """``_get_stg(grid, start, goal, planning_window)`` -> ((stg_x, stg_y), stop).  obstacle: fp32 [m, m] (``local_map[0]``, read
-        in place); goal_map: uint8 [m, m]; collision_map / visited_vis: uint8 [full_w, full_h]; ``.last`` keeps the whole result
-        (with ``taps``: also the last solve's ``trav``, ``goal`` and ``dist`` tensors)."""
+    @property
+    def waves(self) -> int:
+        """``peanut_stg_waves``: the synchronising waves of the last plan this handle took part in."""
+        return int(self._lib.peanut_stg_waves(self._h))
+
+    def _check(self, obstacle, goal_map, collision_map, visited_vis):
         for name, t, dt in (("obstacle", obstacle, torch.float32), ("goal_map", goal_map, torch.uint8),
                             ("collision_map", collision_map, torch.uint8), ("visited_vis", visited_vis, torch.uint8)):
             if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or t.dim() != 2 or t.stride(1) != 1:
@@ -122,6 +125,20 @@ class ShortTermGoal:
         for name, t in (("collision_map", collision_map), ("visited_vis", visited_vis)):
             if tuple(t.shape) != (self.full_w, self.full_h) or not t.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous [{self.full_w}, {self.full_h}] tensor")
+
+    def _set_last(self, res, tap):
+        self.last = dict(stg=(float(res.stg_x), float(res.stg_y)), distance=float(res.distance), stop=bool(res.stop), replan=bool(res.replan),
+                         retried=int(res.retried), n_magnify=int(res.n_magnify), n_solves=int(res.n_solves))
+        if tap[0] is not None:
+            self.last.update(trav=tap[0], goal=tap[1], dist=tap[2])
+        return self.last["stg"], self.last["stop"]
+
+    def get_stg(self, obstacle, goal_map, collision_map, visited_vis, lmb, start_exact, found_goal, goal_name, taps: bool = False):
+        """``_get_stg(grid, start, goal, planning_window)`` -> ((stg_x, stg_y), stop).  obstacle: fp32 [m, m] (``local_map[0]``, read
+        in place); goal_map: uint8 [m, m]; collision_map / visited_vis: uint8 [full_w, full_h]; ``.last`` keeps the whole result
+        (with ``taps``: also the last solve's ``trav``, ``goal`` and ``dist`` tensors)."""
+        self._check(obstacle, goal_map, collision_map, visited_vis)
+        m = self.m
         is_toilet = goal_name == 'toilet'                                  # smaller radius and fewer steps for a toilet (:427-430, :479)
         found = 1 if found_goal == 1 else 0
         start = (C.c_double * 2)(float(start_exact[0]), float(start_exact[1]))
@@ -134,8 +151,52 @@ class ShortTermGoal:
                                            float(getattr(self.args, "magnify_goal_when_hard", 100)), 2 if is_toilet else 8, C.byref(res),
                                            *[None if t is None else t.data_ptr() for t in tap], _lib.current_stream_ptr(self.device))
         _lib.check(rc, "peanut_stg_plan")
-        self.last = dict(stg=(float(res.stg_x), float(res.stg_y)), distance=float(res.distance), stop=bool(res.stop), replan=bool(res.replan),
-                         retried=int(res.retried), n_magnify=int(res.n_magnify), n_solves=int(res.n_solves))
-        if taps:
-            self.last.update(trav=tap[0], goal=tap[1], dist=tap[2])
-        return self.last["stg"], self.last["stop"]
+        return self._set_last(res, tap)
+
+
+def get_stg_batch(planners, inputs, taps: bool = False):
+    """``ShortTermGoal.get_stg`` for E planners in one ``peanut_stg_plan_batch``: the launches and synchronisations of the longest
+    chain among the episodes instead of those of all chains in a row.  ``inputs``: E tuples ``(obstacle, goal_map, collision_map,
+    visited_vis, lmb, start_exact, found_goal, goal_name)`` -> E ``((stg_x, stg_y), stop)`` pairs, every one the bits of the single
+    call; each planner's ``.last`` is set as the single call sets it.  ``ValueError``: an empty batch, more than ``MAX_BATCH``
+    episodes, planners of different sizes, devices, collision radii or step sizes, a planner named twice, a bad tensor."""
+    planners, inputs = list(planners), [tuple(i) for i in inputs]
+    E = len(planners)
+    if E < 1 or E > MAX_BATCH:
+        raise ValueError(f"get_stg_batch takes 1..{MAX_BATCH} episodes, got {E}")
+    if len(inputs) != E or any(len(i) != 8 for i in inputs):
+        raise ValueError("get_stg_batch needs one tuple of the eight get_stg arguments per planner")
+    p0 = planners[0]
+    if len({id(p) for p in planners}) != E:
+        raise ValueError("the same planner appears twice")
+    for e, p in enumerate(planners):
+        if (p.device, p.m, p.full_w, p.full_h, p.col_rad, p.step_size) != (p0.device, p0.m, p0.full_w, p0.full_h, p0.col_rad, p0.step_size):
+            raise ValueError(f"planner {e} differs from planner 0 in device, map sizes, col_rad or step_size: a mixed batch")
+        p._check(*inputs[e][:4])
+        if len(inputs[e][4]) != 4 or len(inputs[e][5]) != 2:
+            raise ValueError(f"episode {e}: lmb must hold four boundaries and start_exact two coordinates")
+    n = p0.m + 2
+    toilet = [i[7] == 'toilet' for i in inputs]
+    tap = [[torch.empty((n, n), dtype=dt, device=p0.device) for dt in (torch.uint8, torch.uint8, torch.float64)] if taps else [None] * 3
+           for _ in range(E)]
+    ptrs = lambda vals: (C.c_void_p * E)(*vals)
+    ints = lambda vals: (C.c_int * E)(*[int(v) for v in vals])
+    res = (_lib.StgResultC * E)()
+    keep = dict(
+        h=ptrs([p._h.value for p in planners]), obstacle=ptrs([i[0].data_ptr() for i in inputs]),
+        row_stride=(C.c_longlong * E)(*[int(i[0].stride(0)) for i in inputs]), goal_map=ptrs([i[1].data_ptr() for i in inputs]),
+        collision=ptrs([i[2].data_ptr() for i in inputs]), visited=ptrs([i[3].data_ptr() for i in inputs]),
+        lmb=(C.c_int * (4 * E))(*[int(v) for i in inputs for v in i[4]]),
+        start_exact=(C.c_double * (2 * E))(*[float(v) for i in inputs for v in i[5]]),
+        found_goal=ints([1 if i[6] == 1 else 0 for i in inputs]), radius_found=ints([6 if t else 8 for t in toilet]),
+        magnify_when_hard=(C.c_double * E)(*[float(getattr(p.args, "magnify_goal_when_hard", 100)) for p in planners]),
+        max_magnify=ints([2 if t else 8 for t in toilet]))
+    desc = _lib.StgBatchC(size=C.sizeof(_lib.StgBatchC), E=E, reserved=0, result_out=res, **keep)
+    if taps:
+        tap_arrays = [ptrs([tap[e][k].data_ptr() for e in range(E)]) for k in range(3)]
+        desc.trav_out, desc.goal_out, desc.dist_out = tap_arrays
+    with torch.cuda.device(p0.device):
+        desc.stream = _lib.current_stream_ptr(p0.device)
+        rc = p0._lib.peanut_stg_plan_batch(C.byref(desc))
+    _lib.check(rc, "peanut_stg_plan_batch")
+    return [p._set_last(res[e], tap[e]) for e, p in enumerate(planners)]

@@ -53,14 +53,17 @@ def run_episode(state: Agent_State, frames: Iterable[Dict], goal_cat: int,
 
 def run_episodes(states, episodes, goal_cats, detector=None,
                  on_step: Optional[Callable[[int, List[Agent_State], List[bool]], None]] = None,
-                 batch_predictions: bool = False, batch_goals: bool = True) -> List[int]:
+                 batch_predictions: bool = False, batch_goals: bool = True, batch_stg: bool = True,
+                 on_group: Optional[Callable] = None) -> List[int]:
     """``run_episode`` for E episodes in lock-step on one device (``Agent_State_Group``): ``states`` E ``Agent_State``
     objects with equal mapping arguments, ``episodes`` E frame sequences in the formats of ``run_episode``, ``goal_cats`` E
     goal categories.  Per step the frames of the episodes still running are formatted, projected and marked as one batch;
     with a ``detector`` that has ``semantic``, they go through ONE ``detector.semantic(rgb[E].flip(-1), ..., goal_cats)``
     call.  Episodes may differ in length: a finished one drops out and the others go on.  ``on_step(i, active_states,
     predicted)`` is called after every step.  ``batch_goals``: the episodes that select a goal on the same step do so in one batched
-    solve (``Agent_State_Group``; the same bits as one by one).  Returns the number of predictions per episode."""
+    solve (``Agent_State_Group``; the same bits as one by one); ``batch_stg``: likewise the short-term goals, for an ``on_step`` that
+    asks the group for them (``group.short_term_goals(infos)``; ``on_group(group)`` hands the group over once, before the first step).
+    Returns the number of predictions per episode."""
     import torch
     from .agent_helper import preprocess_obs_batch
     from .agent_state import Agent_State_Group
@@ -68,7 +71,9 @@ def run_episodes(states, episodes, goal_cats, detector=None,
     iters = [iter(ep) for ep in episodes]
     if not (len(states) == len(iters) == len(goal_cats)):
         raise ValueError(f"{len(states)} states, {len(iters)} episodes and {len(goal_cats)} goal categories")
-    group = Agent_State_Group(states, batch_predictions=batch_predictions, batch_goals=batch_goals)
+    group = Agent_State_Group(states, batch_predictions=batch_predictions, batch_goals=batch_goals, batch_stg=batch_stg)
+    if on_group is not None:
+        on_group(group)
     args = states[0].args
     for s in states:
         s.reset()

@@ -23,7 +23,12 @@ the two sides alternating (A B A B A B: three repeats each, the spread of the th
       host baseline (torch sum, `.cpu()`, the scipy chain scikit-image calls; milliseconds per episode), and the lock-step pipeline
       of (b) with `args.goal_map` off and on.
 
+  (e) the short-term goals in the pipeline (`stg_pipeline`, --plan-stg, written to <out>/plan_stg.jsonl): the pipeline of (b) with
+      `args.goal_map` and `args.plan_stg` on at E = 4 and 8, `Agent_State_Group.short_term_goals` after every step with `batch_stg`
+      off (E `peanut_stg_plan` in a row) and on (one `peanut_stg_plan_batch`), and the same pipeline without the call.
+
     python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only] [--goalmap-only]
+                                   [--plan-stg]
 
 writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
 of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
@@ -392,6 +397,73 @@ def goalmap_pipeline(dev, frames=40, repeats=3, batches=(1, 4, 8)):
     return recs
 
 
+def stg_pipeline(dev, frames=40, repeats=3, batches=(4, 8)):
+    """The lock-step pipeline of `pipeline` with `args.goal_map` and `args.plan_stg` on and the group's `short_term_goals` after every
+    step: `batch_stg` off (E `peanut_stg_plan` in a row) against on (one `peanut_stg_plan_batch`), alternating on ONE set of states,
+    and the same pipeline without the call as the base line."""
+    import gc
+
+    from bench_pipeline import synth_episode
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.peanut_agent import coco_goal_names
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True, goal_map=True, plan_stg=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(batches)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    states = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    name3 = coco_goal_names.get(3, "")
+    sides = {"no_stg": None, "single": False, "batch": True}
+    recs = []
+    for E in batches:
+        goals = [3] * E
+        seen = {}
+
+        def run(side, episodes):
+            holder, out, solves = [], [], []
+
+            def on_step(i, act, predicted):
+                out.append(holder[0].short_term_goals([{"goal_name": name3}] * len(act)))
+                solves.append([s._stg.last["n_solves"] for s in act])
+            if sides[side] is None:
+                run_episodes(states[:E], episodes, goals, detector=det)
+            else:
+                run_episodes(states[:E], episodes, goals, detector=det, on_step=on_step, on_group=holder.append, batch_stg=sides[side])
+                seen[side] = (out, solves, holder[0].stg_batches)
+        for side in sides:
+            run(side, [ep[:12] for ep in eps[:E]])
+        gc.collect()
+        t = {side: [] for side in sides}
+        for _ in range(repeats):
+            for side in sides:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(side, eps[:E])
+                torch.cuda.synchronize()
+                t[side].append(E * frames / (time.perf_counter() - t0))
+        solves = [n for step in seen["batch"][1] for n in step]
+        ms = {side: 1e3 * E / _spread(t[side])["median"] for side in sides}      # per lock-step step of E episodes
+        rec = {"section": "stg_pipeline", "E": E, "frames": frames, "no_stg_steps_per_s": _spread(t["no_stg"]),
+               "batch_stg_off_steps_per_s": _spread(t["single"]), "batch_stg_on_steps_per_s": _spread(t["batch"]),
+               "ms_per_lockstep_step": {k: round(v, 3) for k, v in ms.items()},
+               "stg_adds_ms_per_step": {"single": round(ms["single"] - ms["no_stg"], 3), "batch": round(ms["batch"] - ms["no_stg"], 3)},
+               "stg_batches": [seen["single"][2], seen["batch"][2]], "solves_per_episode_step": {"mean": round(sum(solves) / len(solves), 3), "max": max(solves)},
+               "goals_identical": seen["single"][0] == seen["batch"][0]}
+        print(f"stg pipeline, E = {E}: {rec}", file=sys.stderr, flush=True)
+        recs.append(rec)
+    return recs
+
+
 def _goal_inputs(dev, n, frames=24, cache=None):
     """The goal-selection inputs of n episodes after `frames` frames of the pipeline's synthetic episodes: per episode
     (full_obstacle, collision_map, visited_vis, lmb, loc_rc) in the library's formats, and target_pred.  `cache`: a file to keep
@@ -620,6 +692,8 @@ def main():
     ap.add_argument("--goal-only", action="store_true", help="the goal section alone")
     ap.add_argument("--pipeline-only", action="store_true", help="the pipeline section alone")
     ap.add_argument("--goalmap-only", action="store_true", help="the goalmap section alone -> <out>/goalmap.jsonl")
+    ap.add_argument("--plan-stg", action="store_true",
+                    help="the pipeline with the group's short-term goals after every step, batch_stg off and on -> <out>/plan_stg.jsonl")
     ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
     ap.add_argument("--goal-inputs", default=None, help="file that keeps the goal section's inputs between processes")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
@@ -639,6 +713,12 @@ def main():
             recs += goalmap_pipeline(dev)
         with open(os.path.join(a.out, "goalmap.jsonl"), "w") as f:
             for r in recs:
+                r["device"] = torch.cuda.get_device_name(dev)
+                f.write(json.dumps(r) + "\n")
+        return
+    if a.plan_stg:
+        with open(os.path.join(a.out, "plan_stg.jsonl"), "w") as f:
+            for r in stg_pipeline(dev):
                 r["device"] = torch.cuda.get_device_name(dev)
                 f.write(json.dumps(r) + "\n")
         return

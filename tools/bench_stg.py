@@ -11,6 +11,14 @@ Sides, alternated in one process, medians with spread over ``--repeats`` windows
 * ``magnify4``       a found goal farther than 100 cells with the step limit at four: five solves.
 
     python -m tools.bench_stg [--out profiles/stg/stg.jsonl]
+
+``--batch`` (written to profiles/stg/stg_batch.jsonl): the same map on E DIFFERENT mazes (``maze(seed)``), E = 2, 4, 8 and 16:
+E ``get_stg`` calls in a row against one ``get_stg_batch`` (``peanut_stg_plan_batch``), alternated in one process, milliseconds per
+step of E episodes; and a mixed row at E = 8 -- six plain episodes, one ``retry``, one ``magnify4`` -- through the C ABI on both sides
+(the step limit of four is not a planner argument).  ``earns_default``: the batch median lies below the singles' median by more than
+the min-max spreads of both sides together.
+
+    python -m tools.bench_stg --batch [--out profiles/stg/stg_batch.jsonl]
 """
 from __future__ import annotations
 
@@ -48,14 +56,130 @@ def maze(seed, size=960, window=480):
     return ob, [o, o + window, o, o + window]
 
 
+def batch_rows(a):
+    """The ``--batch`` rows: one per E, then the mixed one."""
+    from peanut_amd import _lib
+    from peanut_amd.agent_state import default_args
+    from peanut_amd.planner import ShortTermGoal, get_stg_batch
+    import workspace_cases as wc
+    dev = torch.device("cuda:0")
+    args = default_args()
+    m, full, emax = 480, 960, 16
+    start = [200.5, 260.25]
+    goal = torch.zeros((m, m), dtype=torch.uint8, device=dev)
+    goal[430, 40] = 1
+    col = torch.zeros((full, full), dtype=torch.uint8, device=dev)
+    vis = torch.zeros((full, full), dtype=torch.uint8, device=dev)
+    obstacles, lmb = [], None
+    for e in range(emax):
+        ob, lmb = maze(e)
+        o = lmb[0]
+        ob[o + 192:o + 209, o + 252:o + 269] = 0
+        obstacles.append(torch.from_numpy(ob).to(dev)[lmb[0]:lmb[1], lmb[2]:lmb[3]])      # views, as local_map[0]
+    fenced = obstacles[6].clone()                                                          # the retry episode of the mixed row
+    fenced[192, 252:269] = fenced[208, 252:269] = 1
+    fenced[192:209, 252] = fenced[192:209, 268] = 1
+    planners = [ShortTermGoal(args, device=dev) for _ in range(emax)]
+    lib = planners[0]._lib
+
+    def measure(sides, calls):
+        for fn in sides.values():
+            fn(2)
+        t = {name: [] for name in sides}
+        for _ in range(a.repeats):
+            for name, fn in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(calls)
+                torch.cuda.synchronize()
+                t[name].append((time.perf_counter() - t0) / calls * 1e3)
+        sp = {k: spread(v) for k, v in t.items()}
+        gain = sp["singles"]["median"] - sp["batch"]["median"]
+        noise = (sp["singles"]["max"] - sp["singles"]["min"]) + (sp["batch"]["max"] - sp["batch"]["min"])
+        return sp, round(sp["singles"]["median"] / sp["batch"]["median"], 3), bool(gain > noise)
+    rows = []
+    calls = max(1, a.calls // 5)
+    for E in (2, 4, 8, 16):
+        ins = [(obstacles[e], goal, col, vis, lmb, start, 0, "chair") for e in range(E)]
+        last = {}
+
+        def singles(n, E=E, ins=ins, last=last):
+            for _ in range(n):
+                for e in range(E):
+                    planners[e].get_stg(*ins[e])
+            last["singles"] = [dict(planners[e].last) for e in range(E)]
+
+        def batch(n, E=E, ins=ins, last=last):
+            for _ in range(n):
+                get_stg_batch(planners[:E], ins)
+            last["batch"] = [dict(planners[e].last) for e in range(E)]
+        sp, ratio, earns = measure({"singles": singles, "batch": batch}, calls)
+        rows.append({"bench": "stg_batch", "E": E, "ms_per_step_of_E": sp, "singles_over_batch": ratio, "earns_default": earns,
+                     "bit_identical": bool(wc.same(last["singles"], last["batch"])), "n_solves": [r["n_solves"] for r in last["batch"]],
+                     "waves": planners[0].waves, "calls": calls})
+    # the mixed row: six plain, one retry, one magnify4 (found goal, step limit four: five solves)
+    E = 8
+    obst = obstacles[:6] + [fenced, obstacles[7]]
+    found, maxmag = [0] * 7 + [1], [8] * 7 + [4]
+    res = (_lib.StgResultC * E)()
+    ptr = lambda vals: (C.c_void_p * E)(*vals)                   # noqa: E731
+    keep = dict(h=ptr([p._h.value for p in planners[:E]]), obstacle=ptr([o.data_ptr() for o in obst]),
+                row_stride=(C.c_longlong * E)(*[int(o.stride(0)) for o in obst]), goal_map=ptr([goal.data_ptr()] * E),
+                collision=ptr([col.data_ptr()] * E), visited=ptr([vis.data_ptr()] * E), lmb=(C.c_int * (4 * E))(*(list(lmb) * E)),
+                start_exact=(C.c_double * (2 * E))(*(start * E)), found_goal=(C.c_int * E)(*found), radius_found=(C.c_int * E)(*[8] * E),
+                magnify_when_hard=(C.c_double * E)(*[100.0] * E), max_magnify=(C.c_int * E)(*maxmag))
+    desc = _lib.StgBatchC(size=C.sizeof(_lib.StgBatchC), E=E, reserved=0, result_out=res, stream=_lib.current_stream_ptr(dev), **keep)
+    one = _lib.StgResultC()
+    bounds, st = (C.c_int * 4)(*lmb), (C.c_double * 2)(*start)
+    last = {}
+
+    def fields(r):
+        return [float(r.stg_x), float(r.stg_y), float(r.distance), int(r.stop), int(r.replan), int(r.retried), int(r.n_magnify), int(r.n_solves)]
+
+    def singles(n):
+        for _ in range(n):
+            out = []
+            for e in range(E):
+                rc = lib.peanut_stg_plan(planners[e]._h, obst[e].data_ptr(), int(obst[e].stride(0)), goal.data_ptr(), col.data_ptr(), vis.data_ptr(),
+                                         C.byref(bounds), C.byref(st), found[e], 8, 100.0, maxmag[e], C.byref(one), None, None, None,
+                                         _lib.current_stream_ptr(dev))
+                _lib.check(rc, "peanut_stg_plan")
+                out.append(fields(one))
+            last["singles"] = out
+
+    def batch(n):
+        for _ in range(n):
+            _lib.check(lib.peanut_stg_plan_batch(C.byref(desc)), "peanut_stg_plan_batch")
+        last["batch"] = [fields(res[e]) for e in range(E)]
+    sp, ratio, earns = measure({"singles": singles, "batch": batch}, calls)
+    rows.append({"bench": "stg_batch_mixed", "E": E, "episodes": "six plain, one retry, one magnify4", "ms_per_step_of_E": sp,
+                 "singles_over_batch": ratio, "earns_default": earns, "bit_identical": last["singles"] == last["batch"],
+                 "n_solves": [r[7] for r in last["batch"]], "waves": planners[0].waves, "calls": calls})
+    for r in rows:
+        r.update(device=torch.cuda.get_device_name(0), local_map=m, col_rad=int(args.col_rad), repeats=a.repeats)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stg", "stg.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batch", action="store_true", help="E single calls against one batched call -> profiles/stg/stg_batch.jsonl")
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=7)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "stg", "stg_batch.jsonl" if a.batch else "stg.jsonl")
     if not torch.cuda.is_available():
         sys.exit("bench_stg measures on the GPU; no device is visible")
+    if a.batch:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        rows = batch_rows(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for row in rows:
+                f.write(json.dumps(row) + "\n")
+                print(json.dumps(row))
+        return
     from peanut_amd import _lib
     from peanut_amd.agent_state import default_args
     from peanut_amd.goal import FMMPlanner, GeodesicSolver
