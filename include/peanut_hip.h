@@ -727,6 +727,63 @@ int peanut_stg_plan_batch(const peanut_stg_batch_t* batch);
 int peanut_stg_waves(peanut_stg_t* h);
 
 /* ------------------------------------------------------------------------------------------
+ * Map datasets on the device (ABI 21; csrc/mapio.hip): the uint8 map sequences nav/collect_maps.py records and
+ * prediction/train_prediction_model.py reads, without the fp32 round trip over the host.
+ * ---------------------------------------------------------------------------------------- */
+#define PEANUT_MAPSEQ_MAX_BATCH 16     /* episodes of one peanut_mapseq_encode */
+#define PEANUT_MAPSEQ_MAX_SAMPLES 64   /* samples of one peanut_mapseq_inputs / peanut_mapseq_bce */
+/* A snapshot per episode of a lock-step group in one launch (collect_maps.py:81-82: `full_map.cpu().numpy() * 255`,
+ * `.astype(np.uint8)`), and the two sums of the dataset filter (:86) from the same pass.  Arguments as a descriptor: `size` =
+ * sizeof(peanut_mapseq_encode_t) first, so that a caller built against another layout is refused; the stream the work is enqueued
+ * on travels in it.  All arrays are HOST arrays of E entries, copied into the launch by value.  src[e]: device fp32 [C, W, H] read
+ * where it lies, plane_stride / row_stride / col_stride in floats (col_stride must be 1); dst[e]: device uint8 [C, W, H],
+ * contiguous; dst = (uint8)(src * 255.0f), one fp32 multiply and a truncation -- numpy's bits for every value in [0, 256/255).
+ * Outside that range the reference is undefined (a float -> uint8 cast that does not fit); here a negative product and NaN give 0,
+ * a product >= 255 gives 255.  sums: DEVICE uint64 [E][2], written whole: [e][0] the sum of the bytes of channels 4:, [e][1] of
+ * channel 1 (exact integers).  Rows whose address and length allow it are read with 16-byte loads, chosen per episode from the
+ * pointers, strides and H.  No synchronisation.  PEANUT_EINVAL with nothing enqueued: a wrong size, E outside
+ * 1..PEANUT_MAPSEQ_MAX_BATCH, C < 5, a null pointer, col_stride != 1, overlapping rows, one dst twice. */
+typedef struct {
+  uint64_t size;                          /* sizeof(peanut_mapseq_encode_t) */
+  int32_t E, C, W, H;
+  const float* const* src;
+  const long long* plane_stride;
+  const long long* row_stride;
+  const long long* col_stride;
+  uint8_t* const* dst;
+  uint64_t* sums;                         /* device [E][2] */
+  void* stream;
+} peanut_mapseq_encode_t;
+int peanut_mapseq_encode(const peanut_mapseq_encode_t* batch);
+/* A stored sequence on the device: maps uint8 [T, C, W, H], contiguous; and the stream the calls that read it are enqueued on
+ * (NULL = default stream). */
+typedef struct {
+  const uint8_t* maps;
+  int32_t T, C, W, H;
+  void* stream;
+} peanut_mapseq_t;
+/* One sample of it: snapshot t_idx, the S x S window whose first cell is (x1, y1). */
+typedef struct {
+  int32_t t_idx, x1, y1;
+} peanut_mapseq_sample_t;
+/* The model inputs of B samples (LoadMapFromFile, train_prediction_model.py:66-68: `maps[t_idx] / 255.` as fp32;
+ * peanut_amd.mapio.model_input): out device fp32 [B, C, S, S] = float(byte) / 255.0f, the IEEE division, bit for bit
+ * np.float32(k) / np.float32(255) for all 256 bytes.  seq and samples are HOST structs (samples: B of them), copied by value.
+ * Enqueued on seq->stream.  No synchronisation.  PEANUT_EINVAL with nothing enqueued: a null pointer, B outside
+ * 1..PEANUT_MAPSEQ_MAX_SAMPLES, S outside 1..min(W, H), a t_idx outside [0, T), a window that leaves the map. */
+int peanut_mapseq_inputs(const peanut_mapseq_t* seq, const peanut_mapseq_sample_t* samples, int B, int S, float* out);
+/* The loss of the reference on B samples (my_loss, train_prediction_model.py:173-184, on the target of :85-89), the target never
+ * materialised: logits device fp32 [B, K, S, S] (raw, no sigmoid); the target of cell (k, i, j) of sample b is
+ * y = float(maps[T-1, 4+k, x1+i, y1+j] * (maps[t_idx, 1, x1+i, y1+j] == 0)) / 255.0f; the loss of a cell, in double on the promoted
+ * x and y, (1 - y) * x + max(-x, 0) + log1p(exp(-|x|)) (binary_cross_entropy_with_logits, reduction 'none').  sum_out: HOST double
+ * [B][K], the sum over the window.  The cells are summed over a fixed partition (chunks of 1024 cells, a function of S alone) in a
+ * fixed order: the bits of sum_out[b][k] depend on neither B, the sample's slot nor the run.  The logits must be finite.
+ * Synchronises seq->stream (the sums come back to the host).  PEANUT_EINVAL with nothing enqueued: as peanut_mapseq_inputs, and K
+ * outside 1..C - 4. */
+int peanut_mapseq_bce(const peanut_mapseq_t* seq, const peanut_mapseq_sample_t* samples, int B, int S, const float* logits, int K,
+                      double* sum_out);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU: collation of the predicted maps for logging.  One process per GPU, maps /
  * episodes sharded with no data-path collective -- the reference shards by hand with --start_ep/--end_ep/
  * --sem_gpu_id (nav/arguments.py:15-20, nav/collect.py:37-50) and never communicates; this all-gather is the one

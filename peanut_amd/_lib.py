@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 20    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 21    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -83,6 +83,27 @@ class StgBatchC(C.Structure):
                 ("radius_found", C.POINTER(C.c_int)), ("magnify_when_hard", C.POINTER(C.c_double)), ("max_magnify", C.POINTER(C.c_int)),
                 ("result_out", C.POINTER(StgResultC)), ("trav_out", C.POINTER(C.c_void_p)), ("goal_out", C.POINTER(C.c_void_p)),
                 ("dist_out", C.POINTER(C.c_void_p)), ("stream", C.c_void_p)]
+
+
+class MapSeqC(C.Structure):
+    """peanut_mapseq_t: a stored uint8 [T,C,W,H] sequence on the device and the stream its readers are enqueued on (32 bytes)."""
+    _fields_ = [("maps", C.c_void_p), ("T", C.c_int32), ("C", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("stream", C.c_void_p)]
+
+
+class MapSeqEncodeC(C.Structure):
+    """peanut_mapseq_encode_t: the descriptor of peanut_mapseq_encode (host arrays of E entries; ``size`` first)."""
+    _fields_ = [("size", C.c_uint64), ("E", C.c_int32), ("C", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("src", C.POINTER(C.c_void_p)), ("plane_stride", C.POINTER(C.c_longlong)), ("row_stride", C.POINTER(C.c_longlong)),
+                ("col_stride", C.POINTER(C.c_longlong)), ("dst", C.POINTER(C.c_void_p)), ("sums", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class MapSeqSampleC(C.Structure):
+    """peanut_mapseq_sample_t: snapshot index and first cell of one sample's window (12 bytes)."""
+    _fields_ = [("t_idx", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
+MAPSEQ_MAX_BATCH = 16      # PEANUT_MAPSEQ_MAX_BATCH
+MAPSEQ_MAX_SAMPLES = 64    # PEANUT_MAPSEQ_MAX_SAMPLES
 
 
 class TensorC(C.Structure):
@@ -182,6 +203,9 @@ SIGNATURES = {
                                   C.c_double, C.c_int, C.POINTER(StgResultC), _P, _P, _P, _P]),
     "peanut_stg_plan_batch": (C.c_int, [C.POINTER(StgBatchC)]),
     "peanut_stg_waves": (C.c_int, [_P]),
+    "peanut_mapseq_encode": (C.c_int, [C.POINTER(MapSeqEncodeC)]),
+    "peanut_mapseq_inputs": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P]),
+    "peanut_mapseq_bce": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_double)]),
     "peanut_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_destroy": (None, [_P]),

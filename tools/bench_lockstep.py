@@ -27,8 +27,13 @@ the two sides alternating (A B A B A B: three repeats each, the spread of the th
       `args.goal_map` and `args.plan_stg` on at E = 4 and 8, `Agent_State_Group.short_term_goals` after every step with `batch_stg`
       off (E `peanut_stg_plan` in a row) and on (one `peanut_stg_plan_batch`), and the same pipeline without the call.
 
+  (f) recording map sequences in the pipeline (`record_maps`, --record-maps, written to profiles/mapio/recorder.jsonl): the lock-step
+      pipeline of (b) with 100-frame episodes (save steps 25, 50, 75, 100 of nav/collect_maps.py:52) without a recorder, with a host
+      recorder built from the route of `mapio.encode_map` (the fp32 full map copied down, two NumPy passes,
+      E times in a row) and with `mapio.MapSequenceRecorder` (one launch per save step, nothing read back during the episode).
+
     python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only] [--goalmap-only]
-                                   [--plan-stg]
+                                   [--plan-stg] [--record-maps]
 
 writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
 of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
@@ -464,6 +469,75 @@ def stg_pipeline(dev, frames=40, repeats=3, batches=(4, 8)):
     return recs
 
 
+def record_maps(dev, frames=100, repeats=3, batches=(4, 8)):
+    """The lock-step pipeline of `pipeline` with no recorder, a host recorder (the fp32 map copied down and encoded with NumPy, per
+    episode) and `mapio.MapSequenceRecorder`, alternating on ONE set of states; steps/s/GPU summed over the episodes.  After the
+    timed runs the two recorders' sequences and keep decisions are compared."""
+    import gc
+
+    import numpy as np
+    from bench_pipeline import synth_episode
+    from peanut_amd import mapio
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(batches)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    states = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    steps = [s for s in mapio.SAVE_STEPS if s <= frames]
+    host_seq = [np.zeros((len(steps), 14, states[0].full_w, states[0].full_h), np.uint8) for _ in range(emax)]
+
+    def host_on_step(i, act, predicted):
+        if i + 1 in steps:
+            for s in act:
+                full_map = s.full_map.cpu().numpy() * 255                         # collect_maps.py:81-82
+                host_seq[states.index(s)][steps.index(i + 1)] = full_map.astype(np.uint8)
+    rec = mapio.MapSequenceRecorder(states, save_steps=steps)
+    sides = {"none": None, "host": host_on_step, "device": rec.on_step}
+    recs = []
+    for E in batches:
+        goals = [3] * E
+        for name in sides:
+            run_episodes(states[:E], [ep[:27] for ep in eps[:E]], goals, detector=det, on_step=sides[name])
+        gc.collect()
+        t = {name: [] for name in sides}
+        for _ in range(repeats):
+            for name in sides:
+                if name == "device":
+                    rec.reset()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run_episodes(states[:E], eps[:E], goals, detector=det, on_step=sides[name])
+                if name == "device":
+                    keeps = [rec.keep(s) for s in states[:E]]                     # the decision is part of the recorder's work
+                elif name == "host":
+                    keeps_host = [mapio.keep_sequence(q) for q in host_seq[:E]]
+                torch.cuda.synchronize()
+                t[name].append(E * frames / (time.perf_counter() - t0))
+        same = all(np.array_equal(rec.sequence(s), host_seq[e]) for e, s in enumerate(states[:E]))
+        ms = {name: 1e3 * E / _spread(t[name])["median"] for name in sides}
+        r = {"section": "record_maps", "E": E, "frames": frames, "save_steps": steps,
+             "no_recorder_steps_per_s": _spread(t["none"]), "host_recorder_steps_per_s": _spread(t["host"]),
+             "device_recorder_steps_per_s": _spread(t["device"]),
+             "ms_per_lockstep_step": {k: round(v, 3) for k, v in ms.items()},
+             "recorder_adds_ms_per_save_step": {k: round((ms[k] - ms["none"]) * frames / len(steps), 3) for k in ("host", "device")},
+             "sequences_equal": bool(same), "keep_equal": keeps == keeps_host, "launches": rec.launches}
+        print(f"record maps, E = {E}: {r}", file=sys.stderr, flush=True)
+        recs.append(r)
+    return recs
+
+
 def _goal_inputs(dev, n, frames=24, cache=None):
     """The goal-selection inputs of n episodes after `frames` frames of the pipeline's synthetic episodes: per episode
     (full_obstacle, collision_map, visited_vis, lmb, loc_rc) in the library's formats, and target_pred.  `cache`: a file to keep
@@ -694,6 +768,8 @@ def main():
     ap.add_argument("--goalmap-only", action="store_true", help="the goalmap section alone -> <out>/goalmap.jsonl")
     ap.add_argument("--plan-stg", action="store_true",
                     help="the pipeline with the group's short-term goals after every step, batch_stg off and on -> <out>/plan_stg.jsonl")
+    ap.add_argument("--record-maps", action="store_true",
+                    help="the pipeline with no recorder, a host recorder and mapio.MapSequenceRecorder -> profiles/mapio/recorder.jsonl")
     ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
     ap.add_argument("--goal-inputs", default=None, help="file that keeps the goal section's inputs between processes")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
@@ -705,6 +781,14 @@ def main():
         return
     if a.goal_trace_child:
         goal_trace_child(dev, a.goal_trace_child, cache=a.goal_inputs)
+        return
+    if a.record_maps:
+        out = os.path.join(ROOT, "profiles", "mapio")
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "recorder.jsonl"), "w") as f:
+            for r in record_maps(dev):
+                r["device"] = torch.cuda.get_device_name(dev)
+                f.write(json.dumps(r) + "\n")
         return
     os.makedirs(a.out, exist_ok=True)
     if a.goalmap_only:
