@@ -18,7 +18,12 @@ def accumulate_instances(pred_masks: torch.Tensor, pred_classes: torch.Tensor, s
                          n_cats: int, sem_pred_prob_thr: float, goal_thr: float,
                          goal_cat: Optional[int]) -> torch.Tensor:
     """segmentation.py:46-60 as one device launch: [n,H,W] bool/uint8 masks, [n] classes, [n] scores
-    -> float32 [H,W,n_cats+1] (channel n_cats stays zero).  No host sync."""
+    -> float32 [H,W,n_cats+1] (channel n_cats stays zero).  No host sync.
+
+    Masks are bool, as detectron2 hands them over, or uint8 holding 0 and 1 only: the kernel adds 1 per covered pixel, where
+    the reference's ``pred_masks[j] * 1.`` would add a uint8 mask's value.  Classes are converted to int32 and scores to float32
+    (what ``pred_instances.scores`` is): both gates compare in float32 against the thresholds narrowed to float32, as torch
+    compares a float32 score with a Python float -- a score equal to float32(threshold) is kept.  1 <= n_cats <= 31."""
     lib = _lib.load()
     if not pred_masks.is_cuda:
         raise _lib.PeanutHipError("accumulate_instances needs HIP tensors (no CPU fallback)")

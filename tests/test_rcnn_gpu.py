@@ -616,6 +616,61 @@ def test_semantic_entry_equals_inference_plus_accumulation(small_net):
         assert torch.equal(got, want)
         assert float(got[..., n_cats].abs().max()) == 0.0
     assert float(net.semantic(img, n_cats, 0.0, 0.0, None).sum()) > 0
+    # ---- the gates of paste_accumulate_kernel ON a detection's score: the thresholds are taken from the scores at run time, a
+    # detection's own score and its float32 successor, so `sc < thr` / `sc < goal_thr` decide about equality.  The expectation
+    # stays accumulate_instances on the pasted masks, which tests/test_frame_glue_gpu.py holds to the reference's loop at the
+    # same boundaries; the difference between the two maps must be the pasted mask of that detection and nothing else.
+    succ = lambda v: float(np.nextafter(np.float32(v), np.float32(2.0)))      # noqa: E731
+
+    def expect(thr, goal_thr, goals):
+        return torch.stack([accumulate_instances(r["pred_masks"], r["pred_classes"], r["scores"], n_cats, thr, goal_thr,
+                                                 None if goals is None else goals[i]) for i, r in enumerate(res)])
+
+    def pasted(score, goals=None):
+        """Per class channel, the pasted masks of the detections whose score is ``score`` (of the frame's goal class only)."""
+        out = torch.zeros((img.shape[0], img.shape[1], img.shape[2], n_cats + 1), device=img.device)
+        for i, r in enumerate(res):
+            for j in range(len(r["scores"])):
+                cls = int(r["pred_classes"][j])
+                if float(r["scores"][j]) == score and 0 <= cls < n_cats and (goals is None or goals[i] == cls):
+                    out[i, :, :, cls] += r["pred_masks"][j].float()
+        return out
+
+    seen = [(i, j, int(r["pred_classes"][j])) for i, r in enumerate(res) for j in range(len(r["scores"]))
+            if bool(r["pred_masks"][j].any()) and 0 <= int(r["pred_classes"][j]) < n_cats]
+    assert seen, "a detection with a non-empty pasted mask"
+    # thr on the score of a detection in the middle of the list, goal gate open
+    i, j, cls = seen[len(seen) // 2]
+    s = float(res[i]["scores"][j])
+    assert float(np.float32(s)) == s < succ(s)
+    at, up = net.semantic(img, n_cats, s, 0.0, None), net.semantic(img, n_cats, succ(s), 0.0, None)
+    assert torch.equal(at, expect(s, 0.0, None)) and torch.equal(up, expect(succ(s), 0.0, None))
+    assert torch.equal(at - up, pasted(s)) and float((at - up)[i, :, :, cls].sum()) >= float(res[i]["pred_masks"][j].sum()) > 0
+    # goal_thr on the score of the top detection of the goal class, thr = 0; the goal lists mix the goal class (present in
+    # frame i), None and a class the frame does not hold
+    tops = [(i, j, c) for i, j, c in seen if c not in [int(k) for k in res[i]["pred_classes"][:j]]]
+    assert tops, "a class whose top detection has a non-empty pasted mask"
+    i, j, g = tops[0]
+    s = float(res[i]["scores"][j])
+    absent = [next((c for c in range(n_cats) if c not in r["pred_classes"].tolist()), n_cats + 3) for r in res]
+    B = len(res)
+    goal_lists = [[g if k == i else None for k in range(B)], [g if k == i else absent[k] for k in range(B)], [g] * B,
+                  [absent[k] if k == i else g for k in range(B)]]
+    for goals in goal_lists:
+        at, up = net.semantic(img, n_cats, 0.0, s, goals), net.semantic(img, n_cats, 0.0, succ(s), goals)
+        assert torch.equal(at, expect(0.0, s, goals)) and torch.equal(up, expect(0.0, succ(s), goals)), goals
+        assert torch.equal(at - up, pasted(s, goals)), goals
+        if goals[i] == g:
+            assert float((at - up)[i, :, :, g].sum()) >= float(res[i]["pred_masks"][j].sum()) > 0, goals
+            assert float((at - up)[i].sum()) == float((at - up)[i, :, :, g].sum())
+    # ... and both gates at one score: goal_thr == thr == the score keeps it, either successor drops it
+    for thr, goal_thr in ((s, s), (succ(s), s), (s, succ(s))):
+        goals = goal_lists[0]
+        assert torch.equal(net.semantic(img, n_cats, thr, goal_thr, goals), expect(thr, goal_thr, goals)), (thr, goal_thr)
+    # the kernel takes the goal categories as a 64-entry argument: a batch of 65 is refused before anything is copied into it
+    from peanut_amd._lib import PeanutHipError
+    with pytest.raises(PeanutHipError, match="1 <= B <= 64"):
+        net.semantic(img[:1].repeat(65, 1, 1, 1), n_cats, 0.0, 0.0, [0] * 65)
 
 
 def test_r101_batch16_full_proposals_against_the_vectorised_oracle():
