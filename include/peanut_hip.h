@@ -727,6 +727,50 @@ int peanut_stg_plan_batch(const peanut_stg_batch_t* batch);
 int peanut_stg_waves(peanut_stg_t* h);
 
 /* ------------------------------------------------------------------------------------------
+ * The planner's map bookkeeping (ABI 22; csrc/plan.hip): what Agent_Helper._plan writes into visited_vis and collision_map on
+ * every step (nav/agent/agent_helper.py:272-315) before _get_stg reads them -- the planner-side sibling of
+ * peanut_map_mark_agent(_batch).  The scalar state machine of _plan (collision test, action choice, untrap) stays the caller's
+ * (peanut_amd.agent_helper.Agent_Helper); the device never sees a float.
+ * ---------------------------------------------------------------------------------------- */
+#define PEANUT_PLAN_LINE_POINTS 26    /* draw_line's steps + 1 */
+#define PEANUT_PLAN_MAX_CELLS 28      /* 4 lengths x 7 widths of the collision loop (:302-303; the reference's width is always 1, :294) */
+#define PEANUT_PLAN_MAX_BATCH 16
+/* HOST only, touches no device: the points of vu.draw_line(last_start, start, .) (nav/agent/utils/visualization.py:19-24):
+ * points_out[i][a] = rint(last_start[a] + (start[a] - last_start[a]) * i / 25) for i = 0..25 -- an integer product, one correctly
+ * rounded division, one add, all in double, and rint to nearest-even: IEEE operations only, NumPy's bits. */
+int peanut_plan_line(const int last_start[2], const int start[2], int points_out[PEANUT_PLAN_LINE_POINTS][2]);
+/* What the calls below share (HOST struct, copied by value): the size of every map and the stream the launch is enqueued on
+ * (NULL = default stream).  For a following peanut_stg_plan / peanut_goal_select_begin to see the marks, give them the same
+ * stream, or one ordered behind it. */
+typedef struct {
+  int32_t full_w, full_h;                 /* 2..65536 */
+  void* stream;
+} peanut_plan_maps_t;
+/* One episode's step (HOST struct, copied by value; the maps are DEVICE uint8 [full_w, full_h], contiguous, distinct). */
+typedef struct {
+  uint8_t* visited_vis;
+  uint8_t* collision_map;
+  int32_t lmb[4];                         /* gx1, gx2, gy1, gy2: an m x m window inside the full map, 2 <= m <= 4096 */
+  int32_t last_start[2];                  /* window cells in [0, m): the last position formed in THIS step's window and thresholded */
+  int32_t start[2];                       /* (:267-277) */
+  int32_t n_cells;                        /* 0..PEANUT_PLAN_MAX_CELLS */
+  int32_t cells_rc[PEANUT_PLAN_MAX_CELLS][2];   /* full-map cells (r, c), already thresholded (:311-314) */
+} peanut_plan_mark_t;
+/* `visited_vis[gx1:gx2, gy1:gy2] = vu.draw_line(last_start, start, visited_vis[gx1:gx2, gy1:gy2])` (:278-280) and
+ * `collision_map[r, c] = 1` for the given cells (:315), in ONE launch: one thread per (line point, corner) and per cell, plain
+ * byte stores of 1, nothing read, no atomics.  Every point (x, y) of peanut_plan_line sets mat[x - 1:x + 1, y - 1:y + 1] = 1 with
+ * Python's slice semantics on the m x m view: rows x - 1 and x, and NOTHING along an axis whose coordinate is 0 (`[-1:1]` is empty
+ * for m >= 2) -- the reference's behaviour, kept.  Enqueued on maps->stream.  No synchronisation, no allocation.
+ * PEANUT_EINVAL with nothing enqueued and no map touched: a null pointer, m < 2, lmb not an m x m window inside the full map, a
+ * start or last_start outside [0, m), n_cells outside its range, a cell outside the map, an episode whose two maps overlap. */
+int peanut_plan_mark(const peanut_plan_maps_t* maps, const peanut_plan_mark_t* episode);
+/* The same for the E episodes of a lock-step group in ONE launch (grid (1, E)): episodes HOST [E].  E outside
+ * 1..PEANUT_PLAN_MAX_BATCH and two episodes naming the same map are refused as well; one refused episode refuses the whole call
+ * and leaves every map as it was.  Every map ends with the bytes E single calls give.  Enqueued on maps->stream.  No
+ * synchronisation, no allocation. */
+int peanut_plan_mark_batch(const peanut_plan_maps_t* maps, int E, const peanut_plan_mark_t* episodes);
+
+/* ------------------------------------------------------------------------------------------
  * Map datasets on the device (ABI 21; csrc/mapio.hip): the uint8 map sequences nav/collect_maps.py records and
  * prediction/train_prediction_model.py reads, without the fp32 round trip over the host.
  * ---------------------------------------------------------------------------------------- */

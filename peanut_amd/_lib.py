@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 21    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 22    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -100,6 +100,22 @@ class MapSeqEncodeC(C.Structure):
 class MapSeqSampleC(C.Structure):
     """peanut_mapseq_sample_t: snapshot index and first cell of one sample's window (12 bytes)."""
     _fields_ = [("t_idx", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
+PLAN_LINE_POINTS = 26      # PEANUT_PLAN_LINE_POINTS
+PLAN_MAX_CELLS = 28        # PEANUT_PLAN_MAX_CELLS
+PLAN_MAX_BATCH = 16        # PEANUT_PLAN_MAX_BATCH
+
+
+class PlanMapsC(C.Structure):
+    """peanut_plan_maps_t: the size of the planner-side maps and the stream the mark is enqueued on (16 bytes)."""
+    _fields_ = [("full_w", C.c_int32), ("full_h", C.c_int32), ("stream", C.c_void_p)]
+
+
+class PlanMarkC(C.Structure):
+    """peanut_plan_mark_t: one episode's step of peanut_plan_mark / peanut_plan_mark_batch."""
+    _fields_ = [("visited_vis", C.c_void_p), ("collision_map", C.c_void_p), ("lmb", C.c_int32 * 4), ("last_start", C.c_int32 * 2),
+                ("start", C.c_int32 * 2), ("n_cells", C.c_int32), ("cells_rc", (C.c_int32 * 2) * PLAN_MAX_CELLS)]
 
 
 MAPSEQ_MAX_BATCH = 16      # PEANUT_MAPSEQ_MAX_BATCH
@@ -203,6 +219,9 @@ SIGNATURES = {
                                   C.c_double, C.c_int, C.POINTER(StgResultC), _P, _P, _P, _P]),
     "peanut_stg_plan_batch": (C.c_int, [C.POINTER(StgBatchC)]),
     "peanut_stg_waves": (C.c_int, [_P]),
+    "peanut_plan_line": (C.c_int, [C.POINTER(C.c_int * 2), C.POINTER(C.c_int * 2), C.POINTER((C.c_int * 2) * PLAN_LINE_POINTS)]),
+    "peanut_plan_mark": (C.c_int, [C.POINTER(PlanMapsC), C.POINTER(PlanMarkC)]),
+    "peanut_plan_mark_batch": (C.c_int, [C.POINTER(PlanMapsC), C.c_int, C.POINTER(PlanMarkC)]),
     "peanut_mapseq_encode": (C.c_int, [C.POINTER(MapSeqEncodeC)]),
     "peanut_mapseq_inputs": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P]),
     "peanut_mapseq_bce": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_double)]),

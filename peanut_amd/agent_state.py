@@ -10,8 +10,8 @@ differences, all on purpose:
 * long-term goal selection (``update_global_goal`` :376-415) runs on the device too (csrc/goal.hip: dilation,
   geodesic field, distance weights and the argmax; scikit-fmm's fast marching replaced by a fixed-point solver of
   the same discretisation).  ``collision_map`` / ``visited_vis``, which the reference
-  reads from ``self.helper`` (the CPU planner's bookkeeping), are attributes here (uint8 HIP tensors, zero until a
-  planner writes them);
+  reads from ``self.helper`` (the CPU planner's bookkeeping), are attributes here (uint8 HIP tensors, zero until
+  ``Agent_Helper`` writes them);
 * ``update_goal_map`` (:418-446: whether the goal category is in the local map, after ``goal_erode`` erosions, a dilation and
   the "no other category claims the cell" mask) and the planner-input dict (:251-257) are here behind ``args.goal_map`` (a
   peanut_amd-only switch, default off): two launches on the local map where it lies (csrc/goal_map.hip) and a 4-byte read-back
@@ -19,7 +19,9 @@ differences, all on purpose:
   is what the reference's ``Agent_Helper.plan_act`` takes;
 * of the local planner, ``_get_stg`` (agent_helper.py:374-493) is here as ``short_term_goal`` behind ``args.plan_stg`` (default
   off, needs ``args.goal_map``; csrc/stg.hip through ``peanut_amd.planner.ShortTermGoal``); the scalar state machine around it
-  (``_plan``: collision and visited bookkeeping, action choice, untrap) stays out.
+  (``_plan``: collision and visited bookkeeping, action choice, untrap) is ``peanut_amd.agent_helper.Agent_Helper``, on the host
+  as in the reference; it writes ``collision_map`` / ``visited_vis`` in place with one launch per step (csrc/plan.hip) and is
+  reached through ``args.plan_act`` (``PEANUT_Agent``) or ``Agent_State_Group.plan_acts``.
 
 The 12-byte pose read-back per step (`local_pose.cpu()`, :276) is kept: the integer cell indices it
 yields drive the host-side decisions exactly as in the reference.  The eight small tensor operations that follow it
@@ -48,7 +50,7 @@ def default_args(**over):
              hfov=79.0, du_scale=1, cat_pred_threshold=5.0, exp_pred_threshold=1.0, map_pred_threshold=0.1,
              camera_height=0.88, min_depth=0.5, max_depth=5.0, sem_pred_prob_thr=0.95, goal_thr=0.985,
              dist_weight_temperature=500, timestep_limit=499, goal_map=False, goal_erode=3, plan_stg=False,
-             magnify_goal_when_hard=100)
+             magnify_goal_when_hard=100, plan_act=False, turn_angle=30, collision_threshold=0.20, move_forward_after_stop=1)
     a.update(over)
     return Namespace(**a)
 
@@ -81,6 +83,10 @@ class Agent_State:
         self.planner_pose_inputs = np.zeros((7))
         self.sem_map_module = Semantic_Mapping(args).to(self.device)
         self.sem_map_module.eval()
+        # preset corner goals of the exploration policy (agent_state.py:79-80); inert at the default switch_step = 0
+        self.global_goal_presets = [(0.1, 0.1), (0.9, 0.1), (0.9, 0.9), (0.1, 0.9)]
+        self.global_goal_preset_id = 0
+        self.helper = None                      # the Agent_Helper that plans for this state, once one is made
         if prediction_model is not None:
             self.prediction_model = prediction_model
         elif getattr(args, "only_explore", 0) == 0:
@@ -429,6 +435,10 @@ class Agent_State:
         return (self.local_map[0], self.goal_map, self.collision_map, self.visited_vis, lmb, start_exact, self.found_goal,
                 infos['goal_name'])
 
+    # ---- agent_state.py:341-342 ----
+    def next_preset_goal(self):
+        self.global_goal_preset_id = (self.global_goal_preset_id + 1) % len(self.global_goal_presets)
+
     # ---- agent_state.py:449-454 ----
     def inc_step(self):
         args = self.args
@@ -464,6 +474,10 @@ class Agent_State:
         if self.l_step == self.args.num_local_steps - 1:
             self.l_step = 0
             self.update_full_map()
+            if self.step < self.args.switch_step:           # no prediction yet: head for a preset corner (:231-237)
+                preset = self.global_goal_presets[self.global_goal_preset_id]
+                self.global_goals = [[int(preset[0] * self.local_w), int(preset[1] * self.local_h)]]
+                self.global_goals = [[min(x, int(self.local_w - 1)), min(y, int(self.local_h - 1))] for x, y in self.global_goals]
 
     def _prediction_due(self):
         """(:240) whether this step predicts and selects a goal."""
@@ -524,6 +538,7 @@ class Agent_State_Group:
         self.goal_map_batches = 0          # peanut_goal_map_batch calls so far (diagnostics)
         self.batch_stg = bool(batch_stg)
         self.stg_batches = 0               # get_stg_batch calls so far (diagnostics)
+        self.plan_batches = 0              # plan_act_batch calls so far (diagnostics)
         self._found_dev = None
         self._found_host = None
         self.sem_map_module = first.sem_map_module
@@ -791,6 +806,28 @@ class Agent_State_Group:
             for s, (stg, stop) in zip(group, res):
                 s.stg, s.stg_stop = stg, stop
         return [(s.stg, s.stg_stop) if getattr(s.args, "plan_stg", False) else None for s in act]
+
+    def plan_acts(self, infos, states=None):
+        """``Agent_Helper.plan_act`` for the active episodes (or ``states``, a subset of them in their order; ``infos`` one per
+        episode) on this step's planner inputs -> one ``{'action': a}`` per episode.  Every state needs its ``Agent_Helper``
+        (``state.helper``) and ``update_goal_map`` to have run on this step.  The episodes that share a planner shape go through
+        ``agent_helper.plan_act_batch``: their marks in ONE ``peanut_plan_mark_batch``, their short-term goals in ONE
+        ``get_stg_batch``; every action, counter and map equals E single ``plan_act`` calls bit for bit.  An episode that is over
+        (its ``timestep`` passed the limit) is simply not passed."""
+        from .agent_helper import plan_act_batch
+        act = list(self.active) if states is None else list(states)
+        if len(infos) != len(act):
+            raise ValueError(f"{len(infos)} infos for {len(act)} episodes")
+        for s in act:
+            if getattr(s, "helper", None) is None:
+                raise RuntimeError("plan_acts needs an Agent_Helper per state (agent_helper.Agent_Helper(args, state))")
+        inputs = {id(s): s.planner_inputs(i, host=False) for s, i in zip(act, infos)}
+        out = {}
+        for group in self._stg_batch(act):
+            for s, a in zip(group, plan_act_batch([s.helper for s in group], [inputs[id(s)] for s in group])):
+                out[id(s)] = a
+            self.plan_batches += 1
+        return [out[id(s)] for s in act]
 
     STG_BATCH_MIN = 2      # the smallest group that goes through get_stg_batch: the batch is faster from E = 2 on (5.5 -> 3.9 ms at 480^2, profiles/stg/stg_batch.jsonl)
 

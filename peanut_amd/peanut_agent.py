@@ -5,11 +5,13 @@ driven by recorded observation tuples instead of a live ``habitat.Env``.
 Per step (peanut_agent.py:38-68): pose change from ``gps`` / ``compass`` -> goal id through ``hm3d_to_coco``
 (constants.py:23-31) -> segmentation + observation formatting (``Agent_Helper.preprocess_inputs``,
 agent_helper.py:166-195; here the HIP detector / mask accumulation / ``peanut_preprocess_obs``) ->
-``Agent_State.init_with_obs`` on the first frame -> ``Agent_State.update_state``.  The local FMM planner that turns
-the planner inputs into a motor action (``Agent_Helper.plan_act``, agent_helper.py:130-159) needs the simulator to
-close the loop and is not part of the hot path; ``act`` therefore returns the planner inputs themselves (with ``args.goal_map``
-on, the reference's whole planner-input dict under ``'planner_inputs'``; with ``args.plan_stg`` on, also what ``_plan`` gets from
-``_get_stg`` on them, under ``'stg'`` and ``'stop'``: ``Agent_State.short_term_goal``)."""
+``Agent_State.init_with_obs`` on the first frame -> ``Agent_State.update_state`` -> ``Agent_Helper.plan_act``
+(agent_helper.py:130-159).  The last step is behind ``args.plan_act`` (a peanut_amd-only switch, default off; needs
+``args.goal_map`` and ``args.plan_stg``): with it ``act`` returns the reference's ``'action'`` beside what it returns without it --
+the planner inputs themselves (with ``args.goal_map`` on, the reference's whole planner-input dict under ``'planner_inputs'``;
+with ``args.plan_stg`` on, also what ``_plan`` gets from ``_get_stg`` on them, under ``'stg'`` and ``'stop'``:
+``Agent_State.short_term_goal``).  With ``plan_act`` on, ``'stg'`` and ``'stop'`` are those of the planner's own solve, which
+sees this step's visited line and collision cells."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -17,7 +19,7 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
-from .agent_helper import preprocess_obs
+from .agent_helper import Agent_Helper, preprocess_obs
 from .agent_state import Agent_State
 from .pose import PoseTracker
 from .segmentation import accumulate_instances
@@ -39,6 +41,11 @@ class PEANUT_Agent:
         self.args = args
         self.agent_states = Agent_State(args, prediction_model=prediction_model, state_dict=state_dict)
         self.device = self.agent_states.device
+        self.agent_helper = None
+        if getattr(args, "plan_act", False):                               # peanut_agent.py:23-24
+            if not (getattr(args, "goal_map", False) and getattr(args, "plan_stg", False)):
+                raise ValueError("args.plan_act needs args.goal_map and args.plan_stg (the planner reads the goal map and the short-term goal)")
+            self.agent_helper = Agent_Helper(args, self.agent_states)
         self.detector = detector
         self.pose = PoseTracker()
         self.first_obs = True
@@ -49,6 +56,8 @@ class PEANUT_Agent:
     # ---- peanut_agent.py:29-36 ----
     def reset(self):
         self.agent_states.reset()
+        if self.agent_helper is not None:
+            self.agent_helper.reset()
         self.pose.reset()
         self.first_obs = True
         self.step = 0
@@ -96,6 +105,8 @@ class PEANUT_Agent:
         info['goal_name'] = hm3d_names[goal]
         goal = hm3d_to_coco[goal]
         self.goal_cat = goal                                               # Agent_Helper.set_goal_cat
+        if self.agent_helper is not None:
+            self.agent_helper.set_goal_cat(goal)
         obs = self._preprocess(observations, goal)
         info['goal_cat_id'] = goal
         if self.first_obs:
@@ -110,5 +121,9 @@ class PEANUT_Agent:
         if getattr(self.args, "plan_stg", False):                          # what _plan gets from _get_stg (agent_helper.py:323)
             if not getattr(self.args, "goal_map", False):
                 raise ValueError("args.plan_stg needs args.goal_map (the short-term goal reads the goal map)")
-            out['stg'], out['stop'] = st.short_term_goal(info)
+            if self.agent_helper is None:
+                out['stg'], out['stop'] = st.short_term_goal(info)
+        if self.agent_helper is not None:                                  # peanut_agent.py:66-68
+            out.update(self.agent_helper.plan_act(st.planner_inputs(info, host=False)))
+            out['stg'], out['stop'] = st.stg, st.stg_stop
         return out

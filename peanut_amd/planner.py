@@ -4,8 +4,9 @@
 dilated goal, geodesic field on the padded grid, the 11 x 11 window pick of ``FMMPlanner.get_short_term_goal``
 (nav/agent/utils/fmm_planner.py:77-116), the eroded retry and the "make the goal larger" loop, all on the maps where they lie on
 the device; the host reads back one 24-byte struct per solve.  The scalar state machine around it (``_plan`` :228-371: collision
-bookkeeping, action choice, untrap) is the caller's, as is ``next_preset_goal()`` when ``last['retried']`` says it is due
-(:444-445).  There is no CPU fallback."""
+bookkeeping, action choice, untrap) is ``peanut_amd.agent_helper.Agent_Helper``, which calls this class once per step and makes
+``next_preset_goal()`` when ``last['retried']`` says it is due (:444-445); a caller that keeps its own planner does both itself.
+There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C

@@ -27,13 +27,17 @@ the two sides alternating (A B A B A B: three repeats each, the spread of the th
       `args.goal_map` and `args.plan_stg` on at E = 4 and 8, `Agent_State_Group.short_term_goals` after every step with `batch_stg`
       off (E `peanut_stg_plan` in a row) and on (one `peanut_stg_plan_batch`), and the same pipeline without the call.
 
+  (g) the motor action in the pipeline (`plan_act_pipeline`, --plan-act, written to profiles/plan/lockstep_plan_act.jsonl): the pipeline
+      of (e) with `batch_stg` on, the motor action off (`short_term_goals` after every step) and on (`plan_acts`: one
+      `peanut_plan_mark_batch`, the same batched short-term goals, the host state machines), alternating on one set of states.
+
   (f) recording map sequences in the pipeline (`record_maps`, --record-maps, written to profiles/mapio/recorder.jsonl): the lock-step
       pipeline of (b) with 100-frame episodes (save steps 25, 50, 75, 100 of nav/collect_maps.py:52) without a recorder, with a host
       recorder built from the route of `mapio.encode_map` (the fp32 full map copied down, two NumPy passes,
       E times in a row) and with `mapio.MapSequenceRecorder` (one launch per save step, nothing read back during the episode).
 
     python tools/bench_lockstep.py [--out profiles/lockstep] [--no-pipeline] [--no-trace] [--goal-only] [--pipeline-only] [--goalmap-only]
-                                   [--plan-stg] [--record-maps]
+                                   [--plan-stg] [--plan-act] [--record-maps]
 
 writes <out>/lockstep.json.  Kernel counts and idle gaps per stage-2 step come from one `rocprofv3 --kernel-trace --stats` run
 of this file's `--trace-child` mode (no counters in that run), summarised under "trace" in the same record."""
@@ -469,6 +473,90 @@ def stg_pipeline(dev, frames=40, repeats=3, batches=(4, 8)):
     return recs
 
 
+def plan_act_pipeline(dev, frames=40, repeats=3, batches=(4, 8)):
+    """The lock-step pipeline of `stg_pipeline` (config 4: detector, projection, prediction, goal selection, goal map, batched short-term
+    goals) with the motor action switched off and on, alternating on ONE set of states: off = `short_term_goals` after every step, the
+    `batch` side of `stg_pipeline`; on = `plan_acts` after every step (one `peanut_plan_mark_batch`, the same batched short-term goals,
+    the host state machines).  The recorded frames do not follow the actions, so most forward actions meet a pose that moved as the
+    recording says.  `off` is also held against the spread recorded for it in <out>/plan_stg.jsonl (reported, not asserted)."""
+    import gc
+
+    import numpy as np
+    from bench_pipeline import synth_episode
+    from peanut_amd.agent_helper import Agent_Helper
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.peanut_agent import coco_goal_names
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True, goal_map=True, plan_stg=True, plan_act=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(batches)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    states = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    helpers = [Agent_Helper(args, s) for s in states]
+    name3 = coco_goal_names.get(3, "")
+    parent = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "lockstep", "plan_stg.jsonl")) as f:
+            for line in f:
+                r = json.loads(line)
+                parent[r["E"]] = r["batch_stg_on_steps_per_s"]
+    except OSError:
+        pass
+    recs = []
+    for E in batches:
+        goals = [3] * E
+        seen = {}
+
+        def run(side, episodes):
+            holder, out = [], []
+
+            def on_step(i, act, predicted):
+                infos = [{"goal_name": name3}] * len(act)
+                if side == "on":
+                    out.append([a["action"] for a in holder[0].plan_acts(infos)])
+                else:
+                    out.append(holder[0].short_term_goals(infos))
+            for h in helpers[:E]:
+                h.reset()
+            np.random.seed(0)
+            run_episodes(states[:E], episodes, goals, detector=det, on_step=on_step, on_group=holder.append)
+            seen[side] = out
+        for side in ("off", "on"):
+            run(side, [ep[:12] for ep in eps[:E]])
+        gc.collect()
+        t = {"off": [], "on": []}
+        for _ in range(repeats):
+            for side in t:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(side, eps[:E])
+                torch.cuda.synchronize()
+                t[side].append(E * frames / (time.perf_counter() - t0))
+        ms = {side: 1e3 * E / _spread(t[side])["median"] for side in t}             # per lock-step step of E episodes
+        actions = [a for step in seen["on"] for a in step]
+        rec = {"section": "plan_act_pipeline", "E": E, "frames": frames, "plan_act_off_steps_per_s": _spread(t["off"]),
+               "plan_act_on_steps_per_s": _spread(t["on"]), "ms_per_lockstep_step": {k: round(v, 3) for k, v in ms.items()},
+               "plan_act_adds_ms_per_step": round(ms["on"] - ms["off"], 3), "actions": {str(a): actions.count(a) for a in sorted(set(actions))},
+               "collision_cells": [int(s.collision_map.sum()) for s in states[:E]], "visited_cells": [int(s.visited_vis.sum()) for s in states[:E]]}
+        if E in parent:
+            med = _spread(t["off"])["median"]
+            rec["parent_off_steps_per_s"] = parent[E]
+            rec["off_inside_parent_spread"] = bool(parent[E]["min"] <= med <= parent[E]["max"])
+        print(f"plan_act pipeline, E = {E}: {rec}", file=sys.stderr, flush=True)
+        recs.append(rec)
+    return recs
+
+
 def record_maps(dev, frames=100, repeats=3, batches=(4, 8)):
     """The lock-step pipeline of `pipeline` with no recorder, a host recorder (the fp32 map copied down and encoded with NumPy, per
     episode) and `mapio.MapSequenceRecorder`, alternating on ONE set of states; steps/s/GPU summed over the episodes.  After the
@@ -768,6 +856,8 @@ def main():
     ap.add_argument("--goalmap-only", action="store_true", help="the goalmap section alone -> <out>/goalmap.jsonl")
     ap.add_argument("--plan-stg", action="store_true",
                     help="the pipeline with the group's short-term goals after every step, batch_stg off and on -> <out>/plan_stg.jsonl")
+    ap.add_argument("--plan-act", action="store_true",
+                    help="the pipeline with the motor action (Agent_State_Group.plan_acts) off and on -> profiles/plan/lockstep_plan_act.jsonl")
     ap.add_argument("--record-maps", action="store_true",
                     help="the pipeline with no recorder, a host recorder and mapio.MapSequenceRecorder -> profiles/mapio/recorder.jsonl")
     ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
@@ -787,6 +877,14 @@ def main():
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "recorder.jsonl"), "w") as f:
             for r in record_maps(dev):
+                r["device"] = torch.cuda.get_device_name(dev)
+                f.write(json.dumps(r) + "\n")
+        return
+    if a.plan_act:
+        out = os.path.join(ROOT, "profiles", "plan")
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "lockstep_plan_act.jsonl"), "w") as f:
+            for r in plan_act_pipeline(dev):
                 r["device"] = torch.cuda.get_device_name(dev)
                 f.write(json.dumps(r) + "\n")
         return
