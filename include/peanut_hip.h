@@ -828,6 +828,94 @@ int peanut_mapseq_bce(const peanut_mapseq_t* seq, const peanut_mapseq_sample_t* 
                       double* sum_out);
 
 /* ------------------------------------------------------------------------------------------
+ * The agent's visualisation frame (ABI 23; csrc/vis.hip): what Agent_Helper._visualize (nav/agent/agent_helper.py:496-621) builds on
+ * the host with PIL, matplotlib, cv2 and scikit-image from maps that live on the device here.  Three launches for 1..16 episodes:
+ * the index map, the ranges of the three fields, the frame.  Nothing synchronises, nothing is allocated.
+ * Unpinned (cv2 is absent where the fixtures are made): the arrow's fill rule and the nearest resize at inexact ratios follow the
+ * rules stated below, not cv2's code; titles are the caller's (they are part of the background image).
+ * ---------------------------------------------------------------------------------------- */
+#define PEANUT_VIS_H 600
+#define PEANUT_VIS_W 1415                  /* init_vis_image: 1165 + 250 (nav/agent/utils/visualization.py:28) */
+#define PEANUT_VIS_FRAME_BYTES 2547000     /* 600 * 1415 * 3: a multiple of 8 */
+#define PEANUT_VIS_MAX_BATCH 16
+#define PEANUT_VIS_RANGE_WORDS 8           /* uint64 words of range workspace per episode */
+/* What the episodes of one call share (HOST struct, copied by value). */
+typedef struct {
+  int32_t m;                     /* the local window is m x m, 1..4096 */
+  int32_t channels;              /* planes of local_map = 4 + num_sem_categories, >= 5 */
+  int32_t full_w, full_h;        /* collision_map / visited_vis are uint8 [full_w, full_h], contiguous */
+  const uint8_t* background;     /* device uint8 [600, 1415, 3] BGR: init_vis_image (visualization.py:27-83) */
+  const uint8_t* palette;        /* device uint8 [256][3] RGB: int(x * 255.) of the colour palette, zero beyond it (:545-550) */
+  const uint8_t* cmap;           /* device uint8 [257][3] BGR: (cm(i)[[2, 1, 0]] * 255).astype(uint8) of 'Purples', entry 256 the
+                                    "bad" colour (:562-567) */
+  void* stream;
+} peanut_vis_common_t;
+/* One episode (HOST struct, copied by value; every pointer a DEVICE pointer). */
+typedef struct {
+  const float* local_map;        /* fp32, `channels` planes of m x m read where they lie (as peanut_goal_map: strides in elements, */
+  long long plane_stride;        /*  column stride 1, planes and rows must not overlap) */
+  long long row_stride;
+  const uint8_t* collision_map;  /* read at lmb (:519) */
+  const uint8_t* visited_vis;    /* (:526) */
+  int32_t lmb[4];                /* gx1, gx2, gy1, gy2: an m x m window inside the full map */
+  const uint8_t* goal;           /* uint8 [m, m], contiguous: the planner's goal map, non-zero = goal (:538-543) */
+  int32_t stg[2];                /* int(self.stg[0]), int(self.stg[1]) (:520-521): marked when both lie below m; a negative
+                                    coordinate in [-m, -1] wraps as NumPy's does; below -m the call is refused */
+  const uint8_t* rgb;            /* uint8 [480, 640, 3] RGB (self.rgb_vis, :556), or NULL: the background stays */
+  const void* target_pred;       /* [m, m] contiguous, or NULL: no overlay, no right panel (:564) */
+  const void* value;             /* [m, m] contiguous (:575); needed with target_pred */
+  const void* dd_wt;             /* [m, m] contiguous (:582); needed with target_pred */
+  int32_t bits[3];               /* 32 (float) or 64 (double) for target_pred, value, dd_wt: the arithmetic of the normalisation */
+  int32_t data_bits[3];          /* 32 or 64: what the field is stored as; fp32 data may be normalised in double (the reference's
+                                    float64 `temp` filled with fp32 predictions, agent_state.py:362), not the reverse */
+  int32_t arrow[4][2];           /* (x, y) frame pixels of get_contour_points (visualization.py:5-16), formed by the caller */
+  uint8_t arrow_bgr[4];          /* the colour of :605-607 (b, g, r, unused) */
+  uint8_t* index_map;            /* out, uint8 [m, m] */
+  uint64_t* ranges;              /* workspace, PEANUT_VIS_RANGE_WORDS words, 8-byte aligned; needs no initialisation */
+  uint8_t* frame;                /* out, uint8 [600, 1415, 3] BGR, 8-byte aligned (peanut_vis_index_map: unused) */
+} peanut_vis_episode_t;
+/* The index map alone, ONE launch (:512-543 and agent_state.py:259-262).  Per cell of the window:
+ *   sem = argmax_c local_map[4 + c], the last plane taken as 1e-5f, the first maximum winning (NaN ranks highest, as torch.argmax)
+ *   sem += 5; a collision cell -> 14; the cell stg -> 15
+ *   no_cat = sem == num_sem_categories + 4:  -> 0; and rint(exp) == 1 -> 2; and rint(obstacle) == 1 -> 1      (in this order)
+ *   visited -> 3; within the disk(4) dilation of goal (cells outside the map unset) -> 4.
+ * With num_sem_categories == 10 the value 14 IS the no-category value, so collision cells fall under those rules: the
+ * reference's behaviour, kept.  Also initialises episode->ranges.  PEANUT_EINVAL with nothing enqueued: a null pointer (rgb and
+ * the three fields may be NULL), m or channels outside their ranges, overlapping strides, lmb not an m x m window inside the full
+ * map, a stg coordinate below -m. */
+int peanut_vis_index_map(const peanut_vis_common_t* common, const peanut_vis_episode_t* episode);
+/* The frame, THREE launches on common->stream:
+ *   1. the index map as above;
+ *   2. the NaN-propagating minimum and maximum of target_pred, value and dd_wt (np.min / np.max: exact, so independent of the
+ *      order of reduction), skipped without a target_pred;
+ *   3. the frame, every thread forming 8 consecutive bytes and storing them as two words:
+ *      the background; rgb flipped to BGR at [50:530, 15:655]; at [50:530, 670:1150] the index map through the palette, flipped
+ *      upside down, BGR, resized to 480 x 480 (:545-557), and where that colour is pure white (b + g + r == 765) and a prediction
+ *      exists the colour of target_pred (:565-572); with a prediction dd_wt at [50:290, 1165:1405], value at [290:530, 1165:1405]
+ *      (240 x 240) and the grey (100) borders of :589-592; the arrow over all of it.
+ *   colour of a field value x: normed = (x - min) / (max - min) in the field's own arithmetic (float or double);
+ *      idx = (int)(normed * 256), 255 where normed == 1; NaN (max == min, or a NaN in the field) -> entry 256.
+ *   resize (cv2's INTER_NEAREST): src = min((int)floor(dst * ifx), n - 1), ifx = 1.0 / ((double)dst_n / src_n), in double.
+ *   arrow: a pixel is painted iff its integer centre lies in the closed polygon of the four vertices -- inside by crossing
+ *      number (even-odd) or on an edge -- in integer arithmetic, clipped to the frame.
+ * PEANUT_EINVAL with nothing enqueued: as peanut_vis_index_map; a target_pred without value or dd_wt; bits or data_bits other than 32 / 64, or bits below data_bits; a
+ * frame or ranges pointer that is not 8-byte aligned; an arrow vertex outside +-2^20. */
+int peanut_vis_render(const peanut_vis_common_t* common, const peanut_vis_episode_t* episode);
+/* The same for E episodes (1..PEANUT_VIS_MAX_BATCH) of one map size in the same three launches (the episode is a grid dimension):
+ * episodes HOST [E]; frame e has the bits of the single call.  Two episodes naming the same frame, index_map or ranges are
+ * refused; one refused episode refuses the whole call and nothing is enqueued. */
+int peanut_vis_render_batch(const peanut_vis_common_t* common, int E, const peanut_vis_episode_t* episodes);
+/* The arg-max of the semantic planes alone (agent_state.py:259-262: `vlm = local_map[4:]; vlm[-1] = 1e-5; vlm.argmax(0)`): out
+ * device uint8 [m, m] in one launch on common->stream; of `common` only m, channels and stream are read; local_map as above.
+ * No synchronisation.  PEANUT_EINVAL: a null pointer, bad dimensions or strides. */
+int peanut_vis_sem_argmax(const peanut_vis_common_t* common, const float* local_map, long long plane_stride, long long row_stride,
+                          uint8_t* out);
+/* Device views into a goal handle (peanut_goal_select's `self.dd_wt` and `self.value`, agent_state.py:409-410): *dd_wt_out and
+ * *value_out point at double [lw, lh] of the last select (value only if that select was given no value_out of its own); dims_out
+ * = {lw, lh}.  No copy, no launch; valid until the next select on the handle.  PEANUT_EINVAL: a null argument, no select yet. */
+int peanut_goal_fields(peanut_goal_t* h, const double** dd_wt_out, const double** value_out, int dims_out[2]);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU: collation of the predicted maps for logging.  One process per GPU, maps /
  * episodes sharded with no data-path collective -- the reference shards by hand with --start_ep/--end_ep/
  * --sem_gpu_id (nav/arguments.py:15-20, nav/collect.py:37-50) and never communicates; this all-gather is the one

@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 22    # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 23   # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -116,6 +116,27 @@ class PlanMarkC(C.Structure):
     """peanut_plan_mark_t: one episode's step of peanut_plan_mark / peanut_plan_mark_batch."""
     _fields_ = [("visited_vis", C.c_void_p), ("collision_map", C.c_void_p), ("lmb", C.c_int32 * 4), ("last_start", C.c_int32 * 2),
                 ("start", C.c_int32 * 2), ("n_cells", C.c_int32), ("cells_rc", (C.c_int32 * 2) * PLAN_MAX_CELLS)]
+
+
+VIS_H, VIS_W = 600, 1415   # PEANUT_VIS_H, PEANUT_VIS_W
+VIS_FRAME_BYTES = 2547000  # PEANUT_VIS_FRAME_BYTES
+VIS_MAX_BATCH = 16         # PEANUT_VIS_MAX_BATCH
+VIS_RANGE_WORDS = 8        # PEANUT_VIS_RANGE_WORDS
+
+
+class VisCommonC(C.Structure):
+    """peanut_vis_common_t: what the episodes of one render share (48 bytes)."""
+    _fields_ = [("m", C.c_int32), ("channels", C.c_int32), ("full_w", C.c_int32), ("full_h", C.c_int32),
+                ("background", C.c_void_p), ("palette", C.c_void_p), ("cmap", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class VisEpisodeC(C.Structure):
+    """peanut_vis_episode_t: one episode of peanut_vis_index_map / peanut_vis_render / peanut_vis_render_batch."""
+    _fields_ = [("local_map", C.c_void_p), ("plane_stride", C.c_longlong), ("row_stride", C.c_longlong),
+                ("collision_map", C.c_void_p), ("visited_vis", C.c_void_p), ("lmb", C.c_int32 * 4), ("goal", C.c_void_p),
+                ("stg", C.c_int32 * 2), ("rgb", C.c_void_p), ("target_pred", C.c_void_p), ("value", C.c_void_p),
+                ("dd_wt", C.c_void_p), ("bits", C.c_int32 * 3), ("data_bits", C.c_int32 * 3), ("arrow", (C.c_int32 * 2) * 4), ("arrow_bgr", C.c_uint8 * 4),
+                ("index_map", C.c_void_p), ("ranges", C.c_void_p), ("frame", C.c_void_p)]
 
 
 MAPSEQ_MAX_BATCH = 16      # PEANUT_MAPSEQ_MAX_BATCH
@@ -222,6 +243,11 @@ SIGNATURES = {
     "peanut_plan_line": (C.c_int, [C.POINTER(C.c_int * 2), C.POINTER(C.c_int * 2), C.POINTER((C.c_int * 2) * PLAN_LINE_POINTS)]),
     "peanut_plan_mark": (C.c_int, [C.POINTER(PlanMapsC), C.POINTER(PlanMarkC)]),
     "peanut_plan_mark_batch": (C.c_int, [C.POINTER(PlanMapsC), C.c_int, C.POINTER(PlanMarkC)]),
+    "peanut_vis_index_map": (C.c_int, [C.POINTER(VisCommonC), C.POINTER(VisEpisodeC)]),
+    "peanut_vis_render": (C.c_int, [C.POINTER(VisCommonC), C.POINTER(VisEpisodeC)]),
+    "peanut_vis_render_batch": (C.c_int, [C.POINTER(VisCommonC), C.c_int, C.POINTER(VisEpisodeC)]),
+    "peanut_vis_sem_argmax": (C.c_int, [C.POINTER(VisCommonC), _P, C.c_longlong, C.c_longlong, _P]),
+    "peanut_goal_fields": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int * 2)]),
     "peanut_mapseq_encode": (C.c_int, [C.POINTER(MapSeqEncodeC)]),
     "peanut_mapseq_inputs": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P]),
     "peanut_mapseq_bce": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_double)]),

@@ -8,7 +8,12 @@
   visited line and the collision cells go into ``Agent_State.visited_vis`` / ``collision_map`` where they lie on the device in one
   launch (``peanut_plan_mark``, csrc/plan.hip), and the short-term goal comes from ``planner.ShortTermGoal`` (csrc/stg.hip).
   ``plan_act_batch`` is the lock-step form: E marks in one ``peanut_plan_mark_batch``, E short-term goals in one
-  ``get_stg_batch``, every action, counter and map the bits of E single calls.  Not here: ``_visualize`` and ``use_gt_seg``.
+  ``get_stg_batch``, every action, counter and map the bits of E single calls.
+* Visualisation (:496-621): with ``args.visualize`` non-zero ``plan_act`` ends with ``_visualize`` (:154-155), which renders the
+  reference's ``vis_image`` on the device (``peanut_amd.vis.VisRenderer``, csrc/vis.hip: three launches, one read-back) and, with
+  ``visualize == 2``, writes it under the reference's file name (PIL, JPEG quality 100).  With ``visualize == 1`` the frame is
+  kept in ``self.vis_image`` and NO window opens (a deviation: no cv2 here).  ``plan_act_batch`` renders its episodes in one
+  ``render_batch``.  Not here: ``use_gt_seg`` (dead code in the reference: it reads ``sem_seg_pred`` before assigning it).
 
 There is no CPU fallback."""
 from __future__ import annotations
@@ -173,10 +178,15 @@ class Agent_Helper:
     ``visited_vis`` ARE the ``Agent_State`` tensors (uint8 HIP, [full_w, full_h]): this class is their writer, goal selection and the
     short-term goal their readers.  ``agent_states.helper`` is set to this object (peanut_agent.py:24)."""
 
-    def __init__(self, args, agent_states):
+    def __init__(self, args, agent_states, rank=0, legend=None):
         self.args = args
         self.agent_states = agent_states
         agent_states.helper = self
+        self.rank = rank
+        self.legend = legend                    # an array or a path (agent_helper.py:102), read when the first frame is rendered
+        self.rgb_vis = None                     # this step's uint8 RGB frame [480, 640, 3] (:222 keeps it as BGR; the device flips)
+        self.vis_image = None
+        self._vis = None
         self.collision_map = agent_states.collision_map
         self.visited_vis = agent_states.visited_vis
         self.col_width = None
@@ -229,8 +239,32 @@ class Agent_Helper:
         self.timestep += 1
         self.goal_name = planner_inputs['goal_name']
         action = self._plan(planner_inputs)
+        if getattr(self.args, "visualize", 0):                      # :154-155
+            self._visualize(planner_inputs)
         self.last_action = action
         return {'action': action}
+
+    # ---- agent_helper.py:496-621 ----
+    def _renderer(self):
+        if self._vis is None:
+            from .vis import VisRenderer
+            self._vis = VisRenderer(self.args, self.agent_states.device, legend=self.legend)
+        return self._vis
+
+    def _visualize(self, planner_inputs):
+        """Render this step's frame on the device and keep it in ``self.vis_image`` (uint8 NumPy [600, 1415, 3], BGR)."""
+        vis = self._renderer()
+        vis.render(**self.agent_states.vis_item(planner_inputs, stg=self.stg, rgb=self.rgb_vis))
+        self._keep_frame(vis.frame_host()[0])
+
+    def _keep_frame(self, frame):
+        self.vis_image = frame = np.array(frame)                     # out of the renderer's pinned buffer: it outlives the step
+        if self.args.visualize == 2:                                 # :615-621
+            import os
+            from .vis import frame_path, write_frame
+            ep_dir, fn = frame_path(self.args, self.rank, self.episode_no, self.timestep)
+            os.makedirs(ep_dir, exist_ok=True)
+            write_frame(fn, frame)
 
     def _plan(self, planner_inputs):
         """(:228-371) one ``peanut_plan_mark``, one short-term goal, the action."""
@@ -389,4 +423,9 @@ def plan_act_batch(helpers, planner_inputs, stg_batch=None):
         action = h._plan_end(p, s, stg, stop)
         h.last_action = action
         out.append({'action': action})
+    if getattr(h0.args, "visualize", 0):                             # the E frames in ONE render_batch and one read-back
+        vis = h0._renderer()
+        vis.render_batch([h.agent_states.vis_item(p, stg=h.stg, rgb=h.rgb_vis) for h, p in zip(helpers, planner_inputs)])
+        for h, frame in zip(helpers, vis.frame_host()):
+            h._keep_frame(frame)
     return out

@@ -101,6 +101,12 @@ class Agent_State:
         self._selem_mask = torch.from_numpy(np.ascontiguousarray(disk(args.col_rad + 1))).to(self.device)     # uint8 [(2R+1)^2]
         self._pose_host = torch.zeros(3, dtype=torch.float32).pin_memory()      # staging of the per-step sensor pose
         self.target_pred = None
+        # what only the visualisation frame reads (agent_state.py:87-88, :409-410), kept with args.visualize: views into the goal solver
+        self.dd_wt = None
+        self.value = None
+        if getattr(args, "visualize", 0) and float(getattr(args, "dist_weight_temperature", 500)) == 0:
+            raise NotImplementedError("args.visualize with dist_weight_temperature == 0: the goal solver keeps no distance weights in "
+                                      "frontier mode, so the frame's two right panels have no source")
         self.global_goals = [[0, 0]]
         self.dist_to_goal = float("inf")
         # long-term goal selection (agent_state.py:376-415); the planner-side maps live here as HIP tensors
@@ -128,6 +134,8 @@ class Agent_State:
         self.goal_map = None
         self.init_map_and_pose()
         self.target_pred = None
+        self.dd_wt = None                       # (agent_state.py:99-101)
+        self.value = None
         self.last_global_goal = None
         self.collision_map.zero_()              # Agent_Helper.reset (agent_helper.py:114-115)
         self.visited_vis.zero_()
@@ -352,6 +360,8 @@ class Agent_State:
     def _goal_result(self, res):
         """The host bookkeeping of ``update_global_goal`` (:410-415) from one ``select`` / ``select_batch`` result."""
         self.value_max = res["value_max"]
+        if getattr(self.args, "visualize", 0):            # self.dd_wt / self.value (:409-410) where the solver left them: no copy
+            self.dd_wt, self.value = self._goal_solver().fields()
         self.goal_rounds = res["rounds"]
         self.goal_passes, self.goal_converged = res["passes"], res["converged"]
         new_global_goal = [res["goal"]]
@@ -392,19 +402,39 @@ class Agent_State:
 
     # ---- agent_state.py:251-257 ----
     def planner_inputs(self, infos, host=True):
-        """The dict ``update_state`` hands to ``Agent_Helper.plan_act`` in the reference (without ``sem_map_pred``, which is
-        visualisation only).  ``host=True``: NumPy with the reference's dtypes and shapes (obstacle / exp_pred float32 copies,
-        goal float64 0/1, pose_pred a copy); ``host=False``: the same keys as HIP tensors / views, nothing copied."""
+        """The dict ``update_state`` hands to ``Agent_Helper.plan_act`` in the reference.  ``host=True``: NumPy with the
+        reference's dtypes and shapes (obstacle / exp_pred float32 copies, goal float64 0/1, pose_pred a copy); ``host=False``: the
+        same keys as HIP tensors / views, nothing copied.  ``sem_map_pred`` (:259-262) is there only with ``args.visualize``:
+        int64 NumPy from one arg-max launch (``peanut_vis_sem_argmax``) with ``host=True``; with ``host=False`` the local map itself,
+        the source the device renderer takes the arg-max from inside its own first launch."""
         if self.goal_map is None:
             raise RuntimeError("planner_inputs needs update_goal_map (args.goal_map) to have run on this step")
+        visualize = bool(getattr(self.args, "visualize", 0))
         if not host:
-            return {'obstacle': self.local_map[0], 'exp_pred': self.local_map[1], 'pose_pred': self.planner_pose_inputs,
-                    'goal': self.goal_map, 'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
-        return {'obstacle': np.ascontiguousarray(self.local_map[0].cpu().numpy()),
-                'exp_pred': np.ascontiguousarray(self.local_map[1].cpu().numpy()),
-                'pose_pred': self.planner_pose_inputs.copy(),
-                'goal': self.goal_map.cpu().numpy().astype(np.float64),
-                'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+            p = {'obstacle': self.local_map[0], 'exp_pred': self.local_map[1], 'pose_pred': self.planner_pose_inputs,
+                 'goal': self.goal_map, 'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+            if visualize:
+                p['sem_map_pred'] = self.local_map
+            return p
+        p = {'obstacle': np.ascontiguousarray(self.local_map[0].cpu().numpy()),
+             'exp_pred': np.ascontiguousarray(self.local_map[1].cpu().numpy()),
+             'pose_pred': self.planner_pose_inputs.copy(),
+             'goal': self.goal_map.cpu().numpy().astype(np.float64),
+             'found_goal': self.found_goal, 'goal_name': infos['goal_name']}
+        if visualize:
+            from .vis import sem_argmax
+            p['sem_map_pred'] = sem_argmax(self.local_map).cpu().numpy().astype(np.int64)
+        return p
+
+    def vis_item(self, planner_inputs, stg=None, rgb=None):
+        """What ``vis.VisRenderer.render`` takes of this episode on this step (``Agent_Helper._visualize``)."""
+        args = self.args
+        gx1, gx2, gy1, gy2 = (int(v) for v in planner_inputs['pose_pred'][3:7])
+        whole = self.full_w == args.prediction_window and self.full_h == args.prediction_window
+        return dict(local_map=self.local_map, collision_map=self.collision_map, visited_vis=self.visited_vis, lmb=[gx1, gx2, gy1, gy2],
+                    goal=planner_inputs['goal'], stg=stg, pose_pred=np.asarray(planner_inputs['pose_pred'], np.float64),
+                    goal_name=planner_inputs['goal_name'], rgb=rgb, target_pred=self.target_pred, value=self.value, dd_wt=self.dd_wt,
+                    target_bits=32 if whole else 64)                    # (:362: a float64 `temp` unless the window is the whole map)
 
     # ---- agent_helper.py:256-266 + 374-493, on the device ----
     def short_term_goal(self, infos):

@@ -1636,4 +1636,15 @@ int peanut_goal_select(peanut_goal_t* g, const float* full_obstacle, const uint8
   return e == hipSuccess ? 0 : fail(PEANUT_EHIP, std::string("peanut_goal_select: ") + hipGetErrorString(e));
 }
 
+// self.dd_wt / self.value (:409-410) where the last select left them: the visualisation frame (vis.hip) reads them in place
+int peanut_goal_fields(peanut_goal_t* g, const double** dd_wt_out, const double** value_out, int dims_out[2]) {
+  if (!g || !dd_wt_out || !value_out || !dims_out) return fail(PEANUT_EINVAL, "peanut_goal_fields: null argument");
+  if (!g->have_last || !g->wt_last.p || !g->value.p)
+    return fail(PEANUT_EINVAL, "peanut_goal_fields: no select has left weights on this handle (frontier mode keeps none)");
+  *dd_wt_out = (const double*)g->wt_last.p;
+  *value_out = (const double*)g->value.p;
+  dims_out[0] = g->last_lw; dims_out[1] = g->last_lh;
+  return 0;
+}
+
 }  // extern "C"

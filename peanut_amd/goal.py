@@ -41,6 +41,14 @@ def _ident(t):
     return ("n", a.__array_interface__["data"][0], a.shape, a.strides, a.dtype.str, a.tobytes())
 
 
+class _DeviceView:
+    """A float64 array in a solver's device memory through ``__cuda_array_interface__``; keeps the solver alive."""
+
+    def __init__(self, owner, ptr, shape):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
 class GeodesicSolver:
     """peanut_goal_t: scratch for one full-map size + the collision-disk radius."""
 
@@ -82,6 +90,15 @@ class GeodesicSolver:
 
     def reset(self):
         _lib.check(self._lib.peanut_goal_reset(self._h), "peanut_goal_reset")
+
+    def fields(self):
+        """``(dd_wt, value)`` of the last select (agent_state.py:409-410) as float64 HIP tensors [lw, lh]: VIEWS of the handle's own
+        buffers (``peanut_goal_fields``), no copy, no launch.  Valid until the next select on this solver; ``value`` is the
+        handle's only if that select was not given a ``want_value`` tensor of its own."""
+        dd, val, dims = C.c_void_p(), C.c_void_p(), (C.c_int * 2)()
+        _lib.check(self._lib.peanut_goal_fields(self._h, C.byref(dd), C.byref(val), C.byref(dims)), "peanut_goal_fields")
+        shape = (int(dims[0]), int(dims[1]))
+        return tuple(torch.as_tensor(_DeviceView(self, p.value, shape), device=self.device) for p in (dd, val))
 
     def select_begin(self, full_obstacle, collision_map, visited_vis, lmb, loc_rc):
         """``peanut_goal_select_begin`` on the current stream: the map inputs of the ``select`` that follows are complete HERE; its

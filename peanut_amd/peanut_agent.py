@@ -108,6 +108,8 @@ class PEANUT_Agent:
         if self.agent_helper is not None:
             self.agent_helper.set_goal_cat(goal)
         obs = self._preprocess(observations, goal)
+        if self.agent_helper is not None and getattr(self.args, "visualize", 0):
+            self.agent_helper.rgb_vis = observations.get("rgb")            # agent_helper.py:222
         info['goal_cat_id'] = goal
         if self.first_obs:
             self.agent_states.init_with_obs(obs, info)

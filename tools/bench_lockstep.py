@@ -557,6 +557,103 @@ def plan_act_pipeline(dev, frames=40, repeats=3, batches=(4, 8)):
     return recs
 
 
+def visualize_pipeline(dev, frames=40, repeats=3, batches=(1, 4, 8)):
+    """The lock-step pipeline of `plan_act_pipeline` (config 4, `plan_acts` after every step) with the visualisation frame, three
+    sides alternating on ONE set of states: `off` = args.visualize 0 (the `on` side of `plan_act_pipeline`; held against the spread
+    recorded for it in profiles/plan/lockstep_plan_act.jsonl -- reported, not asserted); `device` = args.visualize 1 (one
+    `render_batch` and one pinned read-back per lock-step step, nothing written to disk); `host` = args.visualize 0 and, after every
+    step, the reference's host statements (tools/bench_vis.host_frame: the plane downloads, NumPy, PIL, matplotlib, scipy) once per
+    episode."""
+    import gc
+
+    import numpy as np
+    from bench_pipeline import synth_episode
+    from bench_vis import host_frame, host_tables
+    from peanut_amd import vis as pv
+    from peanut_amd.agent_helper import Agent_Helper
+    from peanut_amd.agent_state import Agent_State, default_args
+    from peanut_amd.peanut_agent import coco_goal_names
+    from peanut_amd.prediction import PEANUT_Prediction_Model
+    from peanut_amd.rcnn_weights import RcnnCfg, make_seeded_rcnn_state_dict
+    from peanut_amd.replay import run_episodes
+    from peanut_amd.segmentation import HipDetector
+    from peanut_amd.weights import PredCfg, make_seeded_state_dict
+    args = default_args(only_explore=0, sem_gpu_id=dev.index, pred_precision="fp32", select_goal=True, goal_map=True, plan_stg=True, plan_act=True)
+    model = PEANUT_Prediction_Model(args, state_dict=make_seeded_state_dict(PredCfg(), 0))
+    rcfg = RcnnCfg(score_thresh_test=0.5)
+    det = HipDetector(rcfg, make_seeded_rcnn_state_dict(rcfg, 0), device=dev)
+    emax = max(batches)
+    eps = [synth_episode(1000 + e, frames, dev) for e in range(emax)]
+    for ep in eps:
+        for fr in ep:
+            for k in ("masks", "classes", "scores"):
+                fr.pop(k)
+    states = [Agent_State(args, prediction_model=model) for _ in range(emax)]
+    helpers = [Agent_Helper(args, s) for s in states]
+    g = torch.Generator().manual_seed(1)
+    for h in helpers:
+        h.rgb_vis = (torch.rand((480, 640, 3), generator=g) * 256).to(torch.uint8).to(dev)
+    name3 = coco_goal_names.get(3, "")
+    palette, cm, disk4 = host_tables()
+    background = pv.init_vis_image(name3, None)
+    parent = {}
+    try:
+        with open(os.path.join(ROOT, "profiles", "plan", "lockstep_plan_act.jsonl")) as f:
+            for line in f:
+                r = json.loads(line)
+                parent[r["E"]] = r["plan_act_on_steps_per_s"]
+    except OSError:
+        pass
+    recs = []
+    for E in batches:
+        goals = [3] * E
+        seen = {}
+
+        def run(side, episodes):
+            holder, out = [], []
+            args.visualize = 1 if side == "device" else 0
+
+            def on_step(i, act, predicted):
+                infos = [{"goal_name": name3}] * len(act)
+                out.append([a["action"] for a in holder[0].plan_acts(infos)])
+                if side == "host":
+                    for s in act:
+                        p = s.planner_inputs(infos[0], host=False)
+                        it = s.vis_item(p, stg=s.helper.stg, rgb=s.helper.rgb_vis)
+                        if it["value"] is None:         # (visualize was off on this side: the solver's fields are fetched here)
+                            it["dd_wt"], it["value"] = (None, None) if s.target_pred is None else s._goal_solver().fields()
+                        s.helper.vis_image = host_frame(it, background, palette, args.num_sem_categories, cm, disk4)
+            for h in helpers[:E]:
+                h.reset()
+            np.random.seed(0)
+            run_episodes(states[:E], episodes, goals, detector=det, on_step=on_step, on_group=holder.append)
+            seen[side] = out
+        for side in ("off", "device", "host"):
+            run(side, [ep[:12] for ep in eps[:E]])
+        gc.collect()
+        t = {"off": [], "device": [], "host": []}
+        for _ in range(repeats):
+            for side in t:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(side, eps[:E])
+                torch.cuda.synchronize()
+                t[side].append(E * frames / (time.perf_counter() - t0))
+        args.visualize = 0
+        assert seen["off"] == seen["device"] == seen["host"], "the frame changed an action"
+        ms = {side: 1e3 * E / _spread(t[side])["median"] for side in t}             # per lock-step step of E episodes
+        rec = {"section": "visualize_pipeline", "E": E, "frames": frames, **{f"visualize_{k}_steps_per_s": _spread(v) for k, v in t.items()},
+               "ms_per_lockstep_step": {k: round(v, 3) for k, v in ms.items()},
+               "device_adds_ms_per_step": round(ms["device"] - ms["off"], 3), "host_adds_ms_per_step": round(ms["host"] - ms["off"], 3)}
+        if E in parent:
+            med = _spread(t["off"])["median"]
+            rec["parent_off_steps_per_s"] = parent[E]
+            rec["off_inside_parent_spread"] = bool(parent[E]["min"] <= med <= parent[E]["max"])
+        print(f"visualize pipeline, E = {E}: {rec}", file=sys.stderr, flush=True)
+        recs.append(rec)
+    return recs
+
+
 def record_maps(dev, frames=100, repeats=3, batches=(4, 8)):
     """The lock-step pipeline of `pipeline` with no recorder, a host recorder (the fp32 map copied down and encoded with NumPy, per
     episode) and `mapio.MapSequenceRecorder`, alternating on ONE set of states; steps/s/GPU summed over the episodes.  After the
@@ -858,6 +955,8 @@ def main():
                     help="the pipeline with the group's short-term goals after every step, batch_stg off and on -> <out>/plan_stg.jsonl")
     ap.add_argument("--plan-act", action="store_true",
                     help="the pipeline with the motor action (Agent_State_Group.plan_acts) off and on -> profiles/plan/lockstep_plan_act.jsonl")
+    ap.add_argument("--visualize", action="store_true",
+                    help="the plan_act pipeline with the visualisation frame off, on the device and on the host -> profiles/vis/lockstep_visualize.jsonl")
     ap.add_argument("--record-maps", action="store_true",
                     help="the pipeline with no recorder, a host recorder and mapio.MapSequenceRecorder -> profiles/mapio/recorder.jsonl")
     ap.add_argument("--pipeline-batches", default=",".join(str(b) for b in BATCHES))
@@ -877,6 +976,14 @@ def main():
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "recorder.jsonl"), "w") as f:
             for r in record_maps(dev):
+                r["device"] = torch.cuda.get_device_name(dev)
+                f.write(json.dumps(r) + "\n")
+        return
+    if a.visualize:
+        out = os.path.join(ROOT, "profiles", "vis")
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "lockstep_visualize.jsonl"), "w") as f:
+            for r in visualize_pipeline(dev):
                 r["device"] = torch.cuda.get_device_name(dev)
                 f.write(json.dumps(r) + "\n")
         return
