@@ -365,12 +365,25 @@ inline int wino_gran_for(const ConvLayer& L, int B, int H, int W) {
              ? 256 : 128;
 }
 
-// position-rows the Winograd GEMMs of this layer execute on an input [B,H,W,*]: positions x padded tiles
-inline long long wino_padded_rows(const ConvLayer& L, int B, int H, int W) {
+// A layer's Winograd form on an input [B,H,W,*]: THE description every planner and launcher reads (with wino_gemm_args below)
+struct WinoShape {
+  int gran = 128;                  // row padding per position (wino_gran_for)
+  long long n_tiles = 0;           // tiles per position before padding
+  long long m_pad = 0;             // ... padded to whole `gran`-row GEMM tiles
+  long long rows = 0;              // position-rows the GEMMs execute: positions x m_pad
+  size_t v_floats = 0, m_floats = 0;   // the two scratch tensors (V: transformed input, M: GEMM output)
+  bool accepts_deferred = false;   // the input transform can sum a producer's deferred split-K partial tiles (common.h: DeferredSplit)
+};
+inline WinoShape wino_shape(const ConvLayer& form, int B, int H, int W) {
+  WinoShape s;
   int th, tw;
-  long long n_tiles, m_pad;
-  wino_geometry(B, H, W, L.d.dil, &th, &tw, &n_tiles, &m_pad, wino_gran_for(L, B, H, W), L.wino_m);
-  return (long long)L.wino_np() * m_pad;
+  s.gran = wino_gran_for(form, B, H, W);
+  wino_geometry(B, H, W, form.d.dil, &th, &tw, &s.n_tiles, &s.m_pad, s.gran, form.wino_m);
+  s.rows = (long long)form.wino_np() * s.m_pad;
+  s.v_floats = (size_t)s.rows * form.d.cin;
+  s.m_floats = (size_t)s.rows * form.d.cout;
+  s.accepts_deferred = wino_input_accepts_deferred(B, H, W, form.d.cin, form.d.dil, s.gran, form.wino_m);
+  return s;
 }
 
 // F(6x6) layer with an F(4x4) twin: on small maps the 64 positions each pad their few tiles to a whole GEMM tile and the
@@ -384,28 +397,13 @@ inline const ConvLayer* wino_pick_form(const ConvLayer* L, int B, int H, int W) 
   long long big_rows = 0;
   for (const ConvLayer* c = L; c && c->has_wino; c = c->alt.get()) {
     if (c->wino_m == 4) { f4 = c; continue; }
-    const long long r = wino_padded_rows(*c, B, H, W);
+    const long long r = wino_shape(*c, B, H, W).rows;
     if (!big || r < big_rows || (r == big_rows && c->wino_m < big->wino_m)) { big = c; big_rows = r; }
   }
   if (!f4) return big ? big : L;
   if (!big) return f4;
   // a larger tile has to pay for its larger rounding error: only where it executes at least a tenth less
-  return big_rows * 10 <= wino_padded_rows(*f4, B, H, W) * 9 ? big : f4;
-}
-
-// floats of the two Winograd scratch tensors (V: transformed input, M: GEMM output) for an input [B,H,W,*]
-inline void wino_scratch_floats(const ConvLayer& L, int B, int H, int W, size_t* v, size_t* m) {
-  int th, tw;
-  long long n_tiles, m_pad;
-  wino_geometry(B, H, W, L.d.dil, &th, &tw, &n_tiles, &m_pad, wino_gran_for(L, B, H, W), L.wino_m);
-  *v = (size_t)L.wino_np() * m_pad * L.d.cin;
-  *m = (size_t)L.wino_np() * m_pad * L.d.cout;
-}
-
-// whether this layer, run by launch_conv_layer on an input [B,H,W,*], can sum a producer's deferred split-K partial tiles
-inline bool conv_layer_accepts_deferred(const ConvLayer& L, int B, int H, int W) {
-  if (!L.has_wino || L.d.rs || L.wino.rs) return false;
-  return wino_input_accepts_deferred(B, H, W, L.d.cin, L.d.dil, wino_gran_for(L, B, H, W), L.wino_m);
+  return big_rows * 10 <= wino_shape(*f4, B, H, W).rows * 9 ? big : f4;
 }
 
 // Workspace base a planner builds an op's ConvArgs with: plans are made before the workspace exists, and the route only asks
@@ -413,18 +411,16 @@ inline bool conv_layer_accepts_deferred(const ConvLayer& L, int B, int H, int W)
 // 0 still reads as "present"; never dereferenced.
 static char* const kPlanningBase = reinterpret_cast<char*>((uintptr_t)1 << 12);
 
-// The grouped position GEMM of a layer's Winograd form on an input [B,H,W,*] (V -> M): the ConvArgs launch_conv_layer launches and a
-// planner names the op's kernel by (conv_route; there with planning pointers).  *gran / *m_pad: the geometry it was made for.
-inline ConvArgs wino_gemm_args(const ConvLayer& L, int B, int H, int W, float* v, float* m, float* ws, size_t ws_floats, int* gran, long long* m_pad) {
-  int th, tw;
-  long long n_tiles;
-  *gran = wino_gran_for(L, B, H, W);
-  wino_geometry(B, H, W, L.d.dil, &th, &tw, &n_tiles, m_pad, *gran, L.wino_m);
+// The grouped position GEMM of a layer's Winograd form (V -> M): the ConvArgs every launcher launches and every planner names the
+// op's kernel by (conv_route; there with planning pointers).  m_pad: rows per position (WinoShape::m_pad, or the fused RPN chain's
+// m_pad_total); valid_rows: rows per position that hold tiles (0 = not given), whose padding a kernel may skip.
+inline ConvArgs wino_gemm_args(const ConvLayer& L, long long m_pad, long long valid_rows, float* v, float* m, float* ws, size_t ws_floats) {
   ConvArgs g{};
   g.x = v; g.y = m;
-  g.B = 1; g.H = 1; g.W = (int)std::min<long long>(L.wino_np() * *m_pad, 0x7fffffffLL); g.c1 = L.d.cin; g.c2 = 0; g.Ho = 1; g.Wo = g.W;
+  g.B = 1; g.H = 1; g.W = (int)std::min<long long>(L.wino_np() * m_pad, 0x7fffffffLL); g.c1 = L.d.cin; g.c2 = 0; g.Ho = 1; g.Wo = g.W;
   g.ws = ws; g.ws_floats = ws_floats;
-  g.mt_per_group = (int)(*m_pad / 128); g.w_group_stride = L.wino.rs ? L.wino_group_bytes : L.wino_group_floats;
+  g.mt_per_group = (int)(m_pad / 128); g.group_valid_rows = (int)valid_rows;
+  g.w_group_stride = L.wino.rs ? L.wino_group_bytes : L.wino_group_floats;
   return g;
 }
 // whether launch_conv_layer runs the layer's Winograd form
@@ -439,20 +435,21 @@ inline int launch_conv_layer(const ConvLayer& L, const ConvArgs& a, float* wino_
     if (deferred_in) return fail(PEANUT_EINVAL, L.name + ": the producer deferred its split-K reduce to a layer that cannot sum it");
     return launch_conv(L.d, a, s);
   }
-  int gran, rc;
-  long long m_pad;
-  const ConvArgs g = wino_gemm_args(L, a.B, a.H, a.W, wino_v, wino_m, a.ws, a.ws_floats, &gran, &m_pad);
-  if (L.wino_np() * m_pad > 0x7fffffffLL) return fail(PEANUT_EINVAL, L.name + ": Winograd problem too large");
-  rc = launch_wino_input(a.x, wino_v, a.B, a.H, a.W, L.d.cin, L.d.dil, s, gran, L.wino_m, 0, deferred_in ? produced : nullptr);
+  const WinoShape sh = wino_shape(L, a.B, a.H, a.W);
+  if (sh.rows > 0x7fffffffLL) return fail(PEANUT_EINVAL, L.name + ": Winograd problem too large");
+  // valid rows 0: inherited from the copy this launcher grew from, not a decision (the prediction planner passes its tile count)
+  const ConvArgs g = wino_gemm_args(L, sh.m_pad, 0, wino_v, wino_m, a.ws, a.ws_floats);
+  int rc = launch_wino_input(a.x, wino_v, a.B, a.H, a.W, L.d.cin, L.d.dil, s, sh.gran, L.wino_m, 0, deferred_in ? produced : nullptr);
   if (produced) produced->valid = false;
   if (rc) return rc;
   if ((rc = launch_conv(L.wino, g, s))) return rc;
-  return launch_wino_output(wino_m, L.d.scale, L.d.shift, a.res, a.y, a.B, a.H, a.W, L.d.cout, L.d.dil, L.d.relu, s, gran, L.wino_m);
+  return launch_wino_output(wino_m, L.d.scale, L.d.shift, a.res, a.y, a.B, a.H, a.W, L.d.cout, L.d.dil, L.d.relu, s, sh.gran, L.wino_m);
 }
 
 // ---- workspace arena with liveness-based reuse (offsets are planned on the host) ----
 struct Arena {
   size_t top = 0;
+  size_t high = 0;   // the largest `top` reached (top shrinks on release): the workspace a plan needs
   bool keep_all = false;
   std::vector<std::pair<size_t, size_t>> free_list;  // (offset, size)
   static size_t round_up(size_t n) { return (n + 255) & ~(size_t)255; }
@@ -469,6 +466,7 @@ struct Arena {
     }
     const size_t off = top;
     top += bytes;
+    if (top > high) high = top;
     return off;
   }
   void release(size_t off, size_t bytes) {
@@ -541,5 +539,106 @@ inline int bn_fold_eps(const TensorMap& tm, const std::string& bn, int cout, flo
   }
   return 0;
 }
+
+// What a network asks of every conv layer it builds from its state dict
+struct LayerPolicy {
+  float bn_eps;
+  int precision, conv_algo;
+  int wino_request;    // upload_wino_forms' `requested`: 0 = the forms of the per-shape policy, 4 / 5 / 6 = that form only
+  int wino_min_cin;    // wino_eligible's min_cin_default
+};
+
+// conv weight + (norm | bias) -> ConvLayer with folded scale / shift, kept in `convs`; with conv_algo AUTO an eligible stride-1 3x3
+// layer also gets its Winograd forms.  norm: key of the layer's BatchNorm / FrozenBatchNorm, "" = it has a bias (conv + ".bias").
+// BN(eval): y = x*alpha + beta, alpha = weight/sqrt(var+eps), beta = bias - mean*alpha  (fp32, the
+// form ATen's CPU batch_norm inference uses).
+inline int add_conv_layer(std::vector<std::unique_ptr<ConvLayer>>& convs, const TensorMap& tm, const LayerPolicy& p, const std::string& conv,
+                          const std::string& norm, int cin, int cin_pad, int cout, int k, int stride, int pad, int dil, int relu, ConvLayer** out) {
+  int rc = 0;
+  const int64_t wshape[4] = {cout, cin, k, k};
+  const peanut_tensor* w = tm.get(conv + ".weight", 4, wshape, &rc);
+  if (!w) return rc;
+  std::vector<float> scale(cout, 1.f), shift(cout, 0.f);
+  if (!norm.empty()) {
+    if ((rc = bn_fold_eps(tm, norm, cout, p.bn_eps, scale.data(), shift.data()))) return rc;
+  } else {
+    const int64_t cshape[1] = {cout};
+    const peanut_tensor* b = tm.get(conv + ".bias", 1, cshape, &rc);
+    if (!b) return rc;
+    for (int n = 0; n < cout; ++n) shift[n] = b->data[n];
+  }
+  auto L = std::make_unique<ConvLayer>();
+  L->name = conv;
+  if ((rc = upload_conv(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, k, k, stride, pad, dil, relu, p.precision))) return rc;
+  if (p.conv_algo == PEANUT_ALGO_AUTO && wino_eligible(cin_pad, cout, k, k, stride, pad, dil, p.precision, p.wino_min_cin) &&
+      (rc = upload_wino_forms(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, pad, dil, relu, p.precision, p.wino_request)))
+    return rc;
+  *out = L.get();
+  convs.push_back(std::move(L));
+  return 0;
+}
+
+// A bottleneck block's last conv + norm and its stride-1 shortcut conv + norm as ONE pointwise layer `name` over the channel
+// concatenation [conv2 output (c_a channels) | block input (c_b)]: out = norm_a(conv_a(t2)) + norm_b(conv_b(x)), then ReLU
+// (resnet.py:289-305; detectron2 BottleneckBlock.forward).  The norms' scales are folded into the weights (W' = alpha[n] * W[n][c]),
+// the shifts add up.  One launch instead of two, and the identity tensor (as large as the block output) is neither written nor read back.
+inline int add_fused_pair_layer(std::vector<std::unique_ptr<ConvLayer>>& convs, const TensorMap& tm, const LayerPolicy& p, const std::string& name,
+                                const std::string& conv_a, const std::string& norm_a, const std::string& conv_b, const std::string& norm_b,
+                                int c_a, int c_b, int cout, ConvLayer** out) {
+  int rc = 0;
+  const int64_t was[4] = {cout, c_a, 1, 1}, wbs[4] = {cout, c_b, 1, 1};
+  const peanut_tensor* wa = tm.get(conv_a + ".weight", 4, was, &rc);
+  if (!wa) return rc;
+  const peanut_tensor* wb = tm.get(conv_b + ".weight", 4, wbs, &rc);
+  if (!wb) return rc;
+  std::vector<float> sa(cout), ba(cout), sb(cout), bb(cout);
+  if ((rc = bn_fold_eps(tm, norm_a, cout, p.bn_eps, sa.data(), ba.data()))) return rc;
+  if ((rc = bn_fold_eps(tm, norm_b, cout, p.bn_eps, sb.data(), bb.data()))) return rc;
+  const int cin = c_a + c_b;
+  std::vector<float> w((size_t)cout * cin), shift(cout);
+  for (int n = 0; n < cout; ++n) {
+    for (int c = 0; c < c_a; ++c) w[(size_t)n * cin + c] = sa[n] * wa->data[(size_t)n * c_a + c];
+    for (int c = 0; c < c_b; ++c) w[(size_t)n * cin + c_a + c] = sb[n] * wb->data[(size_t)n * c_b + c];
+    shift[n] = ba[n] + bb[n];
+  }
+  auto L = std::make_unique<ConvLayer>();
+  L->name = name;
+  if ((rc = upload_conv(*L, w.data(), nullptr, shift.data(), cout, cin, cin, 1, 1, 1, 0, 1, 1,
+                        rs_planes_of(p.precision) ? p.precision : PEANUT_PREC_FP32))) return rc;
+  *out = L.get();
+  convs.push_back(std::move(L));
+  return 0;
+}
+
+// A handle's side stream for the ops of a plan that run next to the caller's stream, with its fork / join events.  ensure() is
+// called only when a plan actually forks: a handle that never does creates nothing.
+struct SideStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  ~SideStream() {
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  int ensure() {
+    if (stream) return 0;
+    PEANUT_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    PEANUT_HIP_CHECK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    PEANUT_HIP_CHECK(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    return 0;
+  }
+  // the side stream goes on behind everything enqueued so far on `main`
+  int fork(hipStream_t main) {
+    PEANUT_HIP_CHECK(hipEventRecord(ev_fork, main));
+    PEANUT_HIP_CHECK(hipStreamWaitEvent(stream, ev_fork, 0));
+    return 0;
+  }
+  // `main` goes on behind everything enqueued so far on the side stream
+  int join(hipStream_t main) {
+    PEANUT_HIP_CHECK(hipEventRecord(ev_join, stream));
+    PEANUT_HIP_CHECK(hipStreamWaitEvent(main, ev_join, 0));
+    return 0;
+  }
+};
 
 }  // namespace peanut

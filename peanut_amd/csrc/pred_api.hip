@@ -42,9 +42,7 @@ struct Op {
   bool has_in2 = false, has_res = false;
   double flops = 0;
   double bytes = 0;            // algorithmic HBM bytes: every operand read once, the result written once
-  int wino_mt_per_group = 0;   // OP_WINO_GEMM: 128-row tiles per Winograd position
-  int wino_valid_rows = 0;     // OP_WINO_GEMM: tiles per position before the padding to whole GEMM tiles
-  int wino_gran = 128;         // row padding of the Winograd position GEMMs
+  WinoShape wino;              // OP_WINO_IN / _GEMM / _OUT: the layer's Winograd form on its input (net_common.h)
   // two-stream schedule of the PSP head (build_plan): branch 1 ops run on the handle's side stream; the first of them
   // waits for everything enqueued so far on the caller's stream (fork), join_before makes the caller's stream wait for
   // the side stream before this op
@@ -88,7 +86,7 @@ struct peanut_pred {
   std::vector<std::unique_ptr<ConvLayer>> convs;
   // structure
   ConvLayer* stem[3] = {nullptr, nullptr, nullptr};
-  struct Block { ConvLayer *c1, *c2, *c3, *down, *c3d; };   // c3d: conv3 and the stride-1 downsample as one two-source GEMM (add_fused_c3d)
+  struct Block { ConvLayer *c1, *c2, *c3, *down, *c3d; };   // c3d: conv3 and the stride-1 downsample as one two-source GEMM (net_common.h: add_fused_pair_layer)
   std::vector<std::vector<Block>> layers;
   std::vector<ConvLayer*> ppm;
   ConvLayer* bottleneck = nullptr;     // unfolded form: 3x3 over cat([x, ppm...])
@@ -111,83 +109,14 @@ struct peanut_pred {
   Plan* probe_plan = nullptr;
   std::vector<std::vector<hipEvent_t>> probe_events;  // one vector (n_ops + 1 events) per forward
   std::vector<hipEvent_t> event_pool;
-  // side stream of the two-stream PSP-head schedule (created on first use) and its fork / join events
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  SideStream side;   // of the two-stream PSP-head schedule (created on first use)
   ~peanut_pred() {
     for (auto& v : probe_events) for (auto e : v) (void)hipEventDestroy(e);
     for (auto e : event_pool) (void)hipEventDestroy(e);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (side) (void)hipStreamDestroy(side);
   }
 };
 
 namespace {
-
-int bn_fold(peanut_pred* h, const TensorMap& tm, const std::string& bn, int cout, float* scale, float* shift) {
-  return bn_fold_eps(tm, bn, cout, h->cfg.bn_eps, scale, shift);
-}
-
-// conv weight + (BatchNorm | bias) -> ConvLayer with folded scale/shift.
-// BN(eval): y = x*alpha + beta, alpha = weight/sqrt(var+eps), beta = bias - mean*alpha  (fp32, the
-// form ATen's CPU batch_norm inference uses).
-int add_conv(peanut_pred* h, const TensorMap& tm, const std::string& conv, const std::string& bn, int cin,
-             int cin_pad, int cout, int k, int stride, int pad, int dil, int relu, ConvLayer** out) {
-  int rc = 0;
-  const int64_t wshape[4] = {cout, cin, k, k};
-  const peanut_tensor* w = tm.get(conv + ".weight", 4, wshape, &rc);
-  if (!w) return rc;
-  std::vector<float> scale(cout, 1.f), shift(cout, 0.f);
-  const int64_t cshape[1] = {cout};
-  if (!bn.empty()) {
-    if ((rc = bn_fold(h, tm, bn, cout, scale.data(), shift.data()))) return rc;
-  } else {
-    const peanut_tensor* b = tm.get(conv + ".bias", 1, cshape, &rc); if (!b) return rc;
-    for (int n = 0; n < cout; ++n) shift[n] = b->data[n];
-  }
-  auto L = std::make_unique<ConvLayer>();
-  L->name = conv;
-  rc = upload_conv(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, k, k, stride, pad, dil, relu,
-                   h->cfg.precision);
-  if (rc) return rc;
-  if (h->cfg.conv_algo == PEANUT_ALGO_AUTO && wino_eligible(cin_pad, cout, k, k, stride, pad, dil, h->cfg.precision, 64) &&
-      (rc = upload_wino_forms(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, pad, dil, relu, h->cfg.precision, 0)))
-    return rc;
-  *out = L.get();
-  h->convs.push_back(std::move(L));
-  return 0;
-}
-
-// conv3 + BN3 and the block's stride-1 downsample conv + BN as ONE pointwise layer over the channel concatenation
-// [conv2 output | block input] (resnet.py:289-305: out = bn3(conv3(t2)) + bn_d(conv_d(x)), then ReLU): the BN scales are
-// folded into the weights (W' = alpha[n] * W[n][c]), the shifts add up.  One launch instead of two, and the identity
-// tensor (as large as the block output) is neither written nor read back.
-int add_fused_c3d(peanut_pred* h, const TensorMap& tm, const std::string& blk, int planes, int inplanes, int cout, ConvLayer** out) {
-  int rc = 0;
-  const int64_t w3s[4] = {cout, planes, 1, 1}, wds[4] = {cout, inplanes, 1, 1};
-  const peanut_tensor* w3 = tm.get(blk + ".conv3.weight", 4, w3s, &rc);
-  if (!w3) return rc;
-  const peanut_tensor* wd = tm.get(blk + ".downsample.0.weight", 4, wds, &rc);
-  if (!wd) return rc;
-  std::vector<float> s3(cout), b3(cout), sd(cout), bd(cout);
-  if ((rc = bn_fold(h, tm, blk + ".bn3", cout, s3.data(), b3.data()))) return rc;
-  if ((rc = bn_fold(h, tm, blk + ".downsample.1", cout, sd.data(), bd.data()))) return rc;
-  const int cin = planes + inplanes;
-  std::vector<float> w((size_t)cout * cin), shift(cout);
-  for (int n = 0; n < cout; ++n) {
-    for (int c = 0; c < planes; ++c) w[(size_t)n * cin + c] = s3[n] * w3->data[(size_t)n * planes + c];
-    for (int c = 0; c < inplanes; ++c) w[(size_t)n * cin + planes + c] = sd[n] * wd->data[(size_t)n * inplanes + c];
-    shift[n] = b3[n] + bd[n];
-  }
-  auto L = std::make_unique<ConvLayer>();
-  L->name = blk + ".conv3+downsample";
-  if ((rc = upload_conv(*L, w.data(), nullptr, shift.data(), cout, cin, cin, 1, 1, 1, 0, 1, 1,
-                        rs_planes_of(h->cfg.precision) ? h->cfg.precision : PEANUT_PREC_FP32))) return rc;
-  *out = L.get();
-  h->convs.push_back(std::move(L));
-  return 0;
-}
 
 // One layer object whose weight / scale / shift buffers hold those of `parts` (identical shapes and tilings, fp32
 // path) back to back: a grouped GEMM then takes m-tile group g against block g (ConvArgs::mt_per_group,
@@ -230,13 +159,8 @@ ConvArgs conv_op_args(const peanut_pred* h, const Plan& pl, const Op& op, char* 
   ConvArgs a{};
   a.x = P(op.in); a.y = P(op.out);
   a.ws = P(op.branch ? pl.splitk2 : pl.splitk); a.ws_floats = kSplitKScratchFloats;
-  if (op.kind == OP_WINO_GEMM) {
-    a.B = 1; a.H = 1; a.W = op.in.W; a.c1 = op.in.C; a.c2 = 0; a.Ho = 1; a.Wo = op.in.W;
-    a.mt_per_group = op.wino_mt_per_group;
-    a.group_valid_rows = op.wino_valid_rows;
-    a.w_group_stride = op.conv->wino.rs ? op.conv->wino_group_bytes : op.conv->wino_group_floats;
-    return a;
-  }
+  if (op.kind == OP_WINO_GEMM)      // the tile count as valid rows: waves on a position's padding skip their work (pw256_skip_pad)
+    return wino_gemm_args(*op.conv, op.wino.m_pad, op.wino.n_tiles, P(op.in), P(op.out), a.ws, a.ws_floats);
   a.x2 = op.has_in2 ? P(op.in2) : nullptr;
   a.res = op.has_res ? P(op.res) : nullptr;
   a.B = op.in.B; a.H = op.in.H; a.W = op.in.W;
@@ -266,31 +190,27 @@ void push_conv(Plan& pl, const ConvLayer* L, const Act& in, const Act* in2, cons
   if (wino) L = wino_pick_form(L, in.B, in.H, in.W);
   if (wino) {
     // V = B^T d B  ->  36 grouped GEMMs  ->  A^T M A + BN/residual/ReLU   (winograd.hip)
-    int th, tw;
-    long long n_tiles, m_pad;
+    const WinoShape ws = wino_shape(*L, in.B, in.H, in.W);
     const bool rs_gemm = L->wino.rs != 0;
-    const int gran = wino_gran_for(*L, in.B, in.H, in.W);
-    wino_geometry(in.B, in.H, in.W, L->d.dil, &th, &tw, &n_tiles, &m_pad, gran, L->wino_m);
-    const double np = (double)L->wino_np();
-    const long long npl = L->wino_np();
-    Act v = make_act(*ar, 1, 1, (int)(npl * m_pad), in.C);
-    Act m = make_act(*ar, 1, 1, (int)(npl * m_pad), L->d.cout);
+    const double np = (double)L->wino_np(), n_tiles = (double)ws.n_tiles, m_pad = (double)ws.m_pad;
+    Act v = make_act(*ar, 1, 1, (int)ws.rows, in.C);
+    Act m = make_act(*ar, 1, 1, (int)ws.rows, L->d.cout);
     const std::string fam = L->wino_m == 6 ? "wino6_" : (L->wino_m == 5 ? "wino5_" : "wino_");   // op names / kernel families tell the forms apart
     const std::string tag = "[" + fam;
     Op a; a.kind = OP_WINO_IN; a.name = L->name + tag + "in]"; a.kernel = fam + "input"; a.conv = L; a.in = in; a.out = v;
-    a.wino_gran = gran;
-    a.bytes = (double)in.bytes + np * (double)n_tiles * in.C * 4.0;
+    a.wino = ws;
+    a.bytes = (double)in.bytes + np * n_tiles * in.C * 4.0;
     pl.ops.push_back(a);
     Op g; g.kind = OP_WINO_GEMM; g.name = L->name + tag + "gemm]"; g.conv = L;
-    g.in = v; g.in.W = (int)(npl * m_pad); g.in.C = in.C; g.out = m; g.wino_mt_per_group = (int)(m_pad / 128); g.wino_gran = gran; g.wino_valid_rows = (int)n_tiles;
-    g.flops = 2.0 * np * (double)m_pad * L->d.cout * L->cin_real;     // executed, not the direct-form count
-    g.bytes = np * (double)m_pad * (in.C * 4.0 + L->d.cout * 4.0) +
+    g.in = v; g.out = m; g.wino = ws;
+    g.flops = 2.0 * np * m_pad * L->d.cout * L->cin_real;     // executed, not the direct-form count
+    g.bytes = np * m_pad * (in.C * 4.0 + L->d.cout * 4.0) +
               np * (rs_gemm ? (double)L->wino_group_bytes : (double)L->wino_group_floats * 4);
     pl.ops.push_back(g);
     Op o; o.kind = OP_WINO_OUT; o.name = L->name + tag + "out]"; o.kernel = fam + "output"; o.conv = L; o.in = m; o.out = out;
     if (res) { o.res = *res; o.has_res = true; }
-    o.wino_gran = gran;
-    o.bytes = np * (double)n_tiles * L->d.cout * 4 + (double)out.bytes + (res ? (double)out.bytes : 0.0);
+    o.wino = ws;
+    o.bytes = np * n_tiles * L->d.cout * 4 + (double)out.bytes + (res ? (double)out.bytes : 0.0);
     pl.ops.push_back(o);
     ar->release(v.off, v.bytes);
     ar->release(m.off, m.bytes);
@@ -374,7 +294,7 @@ std::unique_ptr<Plan> build_plan(const peanut_pred* h, int B, int H, int W) {
       {   // conv1's output is read by conv2 alone: its Winograd input transform may sum conv1's split-K partial tiles (common.h: DeferredSplit)
         const Op& win = pl->ops[c1_idx + 1];
         if (opt(OPT_DEFER_SPLITK) != 0 && !h->keep_all && win.kind == OP_WINO_IN && pl->ops[c1_idx].kind == OP_CONV && !win.conv->d.rs &&
-            wino_input_accepts_deferred(t1.B, t1.H, t1.W, t1.C, win.conv->d.dil, win.wino_gran, win.conv->wino_m))
+            win.wino.accepts_deferred)
           pl->ops[c1_idx].defer_ok = true;
       }
       rel(t1);
@@ -540,33 +460,18 @@ std::unique_ptr<Plan> build_plan(const peanut_pred* h, int B, int H, int W) {
     int scale_rows[8];
     op.kernel = conv_kernel_family(conv_route(conv_op_desc(op), conv_op_args(h, *pl, op, kPlanningBase, scale_rows)));
   }
-  return pl;   // pl->bytes (high-water mark) is filled in by get_plan
+  pl->bytes = ar.high;
+  return pl;
 }
 
 }  // namespace
-
-// The arena's `top` can shrink on release; the planner needs the high-water mark.  Recompute it
-// from the ops (every Act the plan references must fit).
-static size_t plan_high_water(const Plan& pl) {
-  size_t hw = 0;
-  auto upd = [&](const Act& a) { if (a.bytes && a.off + Arena::round_up(a.bytes) > hw) hw = a.off + Arena::round_up(a.bytes); };
-  for (const auto& op : pl.ops) {
-    upd(op.in); upd(op.in2); upd(op.res); upd(op.out);
-  }
-  for (const auto& kv : pl.named) upd(kv.second);
-  upd(pl.splitk);
-  upd(pl.splitk2);
-  return hw;
-}
 
 static Plan* get_plan(peanut_pred* h, int B, int H, int W) {
   if (B <= 0 || H < 16 || W < 16) { set_error("forward: need B >= 1 and H, W >= 16"); return nullptr; }
   const std::string key = std::to_string(B) + "x" + std::to_string(H) + "x" + std::to_string(W) + (h->keep_all ? "k" : "");
   auto it = h->plans.find(key);
   if (it == h->plans.end()) {
-    auto pl = build_plan(h, B, H, W);
-    pl->bytes = plan_high_water(*pl);
-    it = h->plans.emplace(key, std::move(pl)).first;
+    it = h->plans.emplace(key, build_plan(h, B, H, W)).first;
   }
   return it->second.get();
 }
@@ -587,7 +492,7 @@ static int run_op(peanut_pred* h, const Plan& pl, const Op& op, const float* in_
       return launch_conv(op.conv->d, a, s);
     }
     case OP_WINO_IN: {
-      const int rc = launch_wino_input(P(op.in), P(op.out), op.in.B, op.in.H, op.in.W, op.in.C, op.conv->d.dil, s, op.wino_gran, op.conv->wino_m, 0,
+      const int rc = launch_wino_input(P(op.in), P(op.out), op.in.B, op.in.H, op.in.W, op.in.C, op.conv->d.dil, s, op.wino.gran, op.conv->wino_m, 0,
                                        h->deferred.valid ? &h->deferred : nullptr);
       h->deferred.valid = false;
       return rc;
@@ -598,7 +503,7 @@ static int run_op(peanut_pred* h, const Plan& pl, const Op& op, const float* in_
     }
     case OP_WINO_OUT:
       return launch_wino_output(P(op.in), op.conv->d.scale, op.conv->d.shift, op.has_res ? P(op.res) : nullptr, P(op.out),
-                                op.out.B, op.out.H, op.out.W, op.out.C, op.conv->d.dil, op.conv->d.relu, s, op.wino_gran, op.conv->wino_m);
+                                op.out.B, op.out.H, op.out.W, op.out.C, op.conv->d.dil, op.conv->d.relu, s, op.wino.gran, op.conv->wino_m);
     case OP_MAXPOOL:
       return launch_maxpool3x3s2(P(op.in), P(op.out), op.in.B, op.in.H, op.in.W, op.in.C, op.out.H, op.out.W, s);
     case OP_PPM_POOL:
@@ -707,11 +612,13 @@ int peanut_pred_create(peanut_pred_t** out, const peanut_pred_cfg* cfg, const pe
   for (int i = 0; i < n; ++i)
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
   int rc;
+  // Winograd forms: the per-shape policy's, from 64 input channels on (net_common.h: wino_eligible)
+  const LayerPolicy policy{cfg->bn_eps, cfg->precision, cfg->conv_algo, 0, 64};
   // stem (resnet.py:591-624): 3x3 s2 -> 3x3 -> 3x3, stem_channels = 64
   const int sc = 64;
-  if ((rc = add_conv(h.get(), tm, "backbone.stem.0", "backbone.stem.1", cfg->in_channels, h->cin_pad, sc / 2, 3, 2, 1, 1, 1, &h->stem[0]))) return rc;
-  if ((rc = add_conv(h.get(), tm, "backbone.stem.3", "backbone.stem.4", sc / 2, sc / 2, sc / 2, 3, 1, 1, 1, 1, &h->stem[1]))) return rc;
-  if ((rc = add_conv(h.get(), tm, "backbone.stem.6", "backbone.stem.7", sc / 2, sc / 2, sc, 3, 1, 1, 1, 1, &h->stem[2]))) return rc;
+  if ((rc = add_conv_layer(h->convs, tm, policy, "backbone.stem.0", "backbone.stem.1", cfg->in_channels, h->cin_pad, sc / 2, 3, 2, 1, 1, 1, &h->stem[0]))) return rc;
+  if ((rc = add_conv_layer(h->convs, tm, policy, "backbone.stem.3", "backbone.stem.4", sc / 2, sc / 2, sc / 2, 3, 1, 1, 1, 1, &h->stem[1]))) return rc;
+  if ((rc = add_conv_layer(h->convs, tm, policy, "backbone.stem.6", "backbone.stem.7", sc / 2, sc / 2, sc, 3, 1, 1, 1, 1, &h->stem[2]))) return rc;
   const int stage_blocks[4] = {3, 4, 6, 3};  // ResNet.arch_settings[50] (resnet.py:386-392)
   int inplanes = sc;
   for (int li = 0; li < 4; ++li) {
@@ -723,15 +630,16 @@ int peanut_pred_create(peanut_pred_t** out, const peanut_pred_cfg* cfg, const pe
       const std::string p = "backbone.layer" + std::to_string(li + 1) + "." + std::to_string(bi);
       const int s = bi == 0 ? stride : 1, d = bi == 0 ? first_dil : dilation;
       peanut_pred::Block b{nullptr, nullptr, nullptr, nullptr, nullptr};
-      if ((rc = add_conv(h.get(), tm, p + ".conv1", p + ".bn1", inplanes, inplanes, planes, 1, 1, 0, 1, 1, &b.c1))) return rc;
-      if ((rc = add_conv(h.get(), tm, p + ".conv2", p + ".bn2", planes, planes, planes, 3, s, d, d, 1, &b.c2))) return rc;
+      if ((rc = add_conv_layer(h->convs, tm, policy, p + ".conv1", p + ".bn1", inplanes, inplanes, planes, 1, 1, 0, 1, 1, &b.c1))) return rc;
+      if ((rc = add_conv_layer(h->convs, tm, policy, p + ".conv2", p + ".bn2", planes, planes, planes, 3, s, d, d, 1, &b.c2))) return rc;
       // conv3: BN only; the block's final ReLU follows the residual add and is fused here
-      if ((rc = add_conv(h.get(), tm, p + ".conv3", p + ".bn3", planes, planes, planes * 4, 1, 1, 0, 1, 1, &b.c3))) return rc;
+      if ((rc = add_conv_layer(h->convs, tm, policy, p + ".conv3", p + ".bn3", planes, planes, planes * 4, 1, 1, 0, 1, 1, &b.c3))) return rc;
       if (bi == 0 && (stride != 1 || inplanes != planes * 4)) {
-        if ((rc = add_conv(h.get(), tm, p + ".downsample.0", p + ".downsample.1", inplanes, inplanes, planes * 4, 1, stride, 0, 1, 0, &b.down))) return rc;
+        if ((rc = add_conv_layer(h->convs, tm, policy, p + ".downsample.0", p + ".downsample.1", inplanes, inplanes, planes * 4, 1, stride, 0, 1, 0, &b.down))) return rc;
         // conv_algo AUTO only: DIRECT keeps the reference's op-for-op form (conv3 -> BN, downsample -> BN, add, ReLU)
         if (cfg->conv_algo == PEANUT_ALGO_AUTO && s == 1 && planes % 32 == 0 && inplanes % 32 == 0 && conv_pw_enabled() &&
-            (rc = add_fused_c3d(h.get(), tm, p, planes, inplanes, planes * 4, &b.c3d)))
+            (rc = add_fused_pair_layer(h->convs, tm, policy, p + ".conv3+downsample", p + ".conv3", p + ".bn3", p + ".downsample.0", p + ".downsample.1",
+                                       planes, inplanes, planes * 4, &b.c3d)))
           return rc;
       }
       blocks.push_back(b);
@@ -745,12 +653,12 @@ int peanut_pred_create(peanut_pred_t** out, const peanut_pred_cfg* cfg, const pe
     if (cfg->pool_scales[i] < 1) return fail(PEANUT_EINVAL, "pool_scales must be >= 1");
     const std::string p = "decode_head.psp_modules." + std::to_string(i) + ".1";
     ConvLayer* L;
-    if ((rc = add_conv(h.get(), tm, p + ".conv", p + ".bn", inplanes, inplanes, hc, 1, 1, 0, 1, 1, &L))) return rc;
+    if ((rc = add_conv_layer(h->convs, tm, policy, p + ".conv", p + ".bn", inplanes, inplanes, hc, 1, 1, 0, 1, 1, &L))) return rc;
     h->ppm.push_back(L);
   }
   const int cat = inplanes + cfg->n_pool_scales * hc;
   if (!cfg->fold_ppm) {
-    if ((rc = add_conv(h.get(), tm, "decode_head.bottleneck.conv", "decode_head.bottleneck.bn", cat, cat, hc, 3, 1, 1, 1, 1, &h->bottleneck))) return rc;
+    if ((rc = add_conv_layer(h->convs, tm, policy, "decode_head.bottleneck.conv", "decode_head.bottleneck.bn", cat, cat, hc, 3, 1, 1, 1, 1, &h->bottleneck))) return rc;
   } else {
     // Split W[hc][cat][3][3] into the x part (conv proper) and one folded 1x1 table-builder per scale:
     //   Wq_s[(tap*hc + n)][c] = alpha[n] * W[n][feat + s*hc + c][tap]   (alpha = BN scale, so that the
@@ -759,7 +667,7 @@ int peanut_pred_create(peanut_pred_t** out, const peanut_pred_cfg* cfg, const pe
     const peanut_tensor* w = tm.get("decode_head.bottleneck.conv.weight", 4, wshape, &rc);
     if (!w) return rc;
     std::vector<float> scale(hc), shift(hc);
-    if ((rc = bn_fold(h.get(), tm, "decode_head.bottleneck.bn", hc, scale.data(), shift.data()))) return rc;
+    if ((rc = bn_fold_eps(tm, "decode_head.bottleneck.bn", hc, cfg->bn_eps, scale.data(), shift.data()))) return rc;
     std::vector<float> wx((size_t)hc * inplanes * 9);
     for (int n = 0; n < hc; ++n)
       memcpy(&wx[(size_t)n * inplanes * 9], &w->data[(size_t)n * cat * 9], (size_t)inplanes * 9 * sizeof(float));
@@ -788,7 +696,7 @@ int peanut_pred_create(peanut_pred_t** out, const peanut_pred_cfg* cfg, const pe
       h->convs.push_back(std::move(L));
     }
   }
-  if ((rc = add_conv(h.get(), tm, "decode_head.conv_seg", "", hc, hc, cfg->num_classes, 1, 1, 0, 1, 0, &h->conv_seg))) return rc;
+  if ((rc = add_conv_layer(h->convs, tm, policy, "decode_head.conv_seg", "", hc, hc, cfg->num_classes, 1, 1, 0, 1, 0, &h->conv_seg))) return rc;
   if (cfg->fold_ppm) {
     h->ppm_grouped = build_grouped(h->ppm, "decode_head.psp_modules.*.1.conv", &rc);
     if (rc) return rc;
@@ -862,22 +770,12 @@ int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, i
   if (!h->probe) {
     bool two_streams = false;
     for (const auto& op : pl->ops) two_streams |= op.branch != 0;
-    if (two_streams && !h->side) {
-      PEANUT_HIP_CHECK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-      PEANUT_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-      PEANUT_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
+    if (two_streams && (rc = h->side.ensure())) return rc;
     auto enqueue = [&]() -> int {
       for (const auto& op : pl->ops) {
-        if (op.fork_before) {
-          PEANUT_HIP_CHECK(hipEventRecord(h->ev_fork, s));
-          PEANUT_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        }
-        if (op.join_before) {
-          PEANUT_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
-          PEANUT_HIP_CHECK(hipStreamWaitEvent(s, h->ev_join, 0));
-        }
-        if (int r = run_op(h, *pl, op, in_dev, out_dev, apply_sigmoid, op.branch ? h->side : s)) return r;
+        if (op.fork_before) if (int r = h->side.fork(s)) return r;
+        if (op.join_before) if (int r = h->side.join(s)) return r;
+        if (int r = run_op(h, *pl, op, in_dev, out_dev, apply_sigmoid, op.branch ? h->side.stream : s)) return r;
       }
       return 0;
     };
@@ -991,8 +889,8 @@ int peanut_conv_forward(peanut_conv_t* c, const float* x, const float* x2, int c
   if (int rc = c->ws.ensure(kSplitKScratchFloats * sizeof(float))) return rc;
   a.ws = (float*)c->ws.p; a.ws_floats = kSplitKScratchFloats;
   if (c->L.has_wino && !x2) {
-    size_t vf, mf;
-    wino_scratch_floats(c->L, B, H, W, &vf, &mf);
+    const WinoShape sh = wino_shape(c->L, B, H, W);
+    const size_t vf = sh.v_floats, mf = sh.m_floats;
     // growing a scratch buffer frees the old one: make sure no earlier launch still uses it
     if (vf * sizeof(float) > c->wino_v.bytes || mf * sizeof(float) > c->wino_m.bytes) PEANUT_HIP_CHECK(hipDeviceSynchronize());
     if (int rc = c->wino_v.ensure(vf * sizeof(float))) return rc;

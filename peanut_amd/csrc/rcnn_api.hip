@@ -200,37 +200,6 @@ int rcnn_wino_request() {
   return (m >= 4 && m <= 6) ? m : 0;
 }
 
-int add_rconv(peanut_rcnn* h, const TensorMap& tm, const std::string& name, int cin, int cin_pad, int cout, int k,
-              int stride, int pad, bool norm, int relu, ConvLayer** out) {
-  int rc = 0;
-  const int64_t wshape[4] = {cout, cin, k, k};
-  const peanut_tensor* w = tm.get(name + ".weight", 4, wshape, &rc);
-  if (!w) return rc;
-  std::vector<float> scale(cout, 1.f), shift(cout, 0.f);
-  if (norm) {
-    if ((rc = bn_fold_eps(tm, name + ".norm", cout, h->cfg.bn_eps, scale.data(), shift.data()))) return rc;
-  } else {
-    const int64_t cshape[1] = {cout};
-    const peanut_tensor* b = tm.get(name + ".bias", 1, cshape, &rc);
-    if (!b) return rc;
-    for (int n = 0; n < cout; ++n) shift[n] = b->data[n];
-  }
-  auto L = std::make_unique<ConvLayer>();
-  L->name = name;
-  if ((rc = upload_conv(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, k, k, stride, pad, 1, relu,
-                        h->cfg.precision)))
-    return rc;
-  // fp32 kernels: the prediction planner's forms (F(6x6) with an F(4x4) twin, chosen per shape in push_rconv; the position
-  // GEMMs accumulate in two levels, net_common.h); emulated modes: F(4x4)
-  if (h->cfg.conv_algo == PEANUT_ALGO_AUTO && wino_eligible(cin_pad, cout, k, k, stride, pad, 1, h->cfg.precision) &&
-      (rc = upload_wino_forms(*L, w->data, scale.data(), shift.data(), cout, cin, cin_pad, pad, 1, relu, h->cfg.precision,
-                              rs_planes_of(h->cfg.precision) ? 4 : rcnn_wino_request())))
-    return rc;
-  *out = L.get();
-  h->convs.push_back(std::move(L));
-  return 0;
-}
-
 // BasicStem's 7x7 stride-2 pad-3 conv over 3 channels restated on the 2x2 space-to-depth image (rcnn_preprocess_s2d_kernel):
 // output (oy, ox) reads input rows 2 oy + ky - 3; in blocks of two rows that is block oy + by - 2, row dy inside it, with
 // ky = 2 by + dy - 1 (by = 0..3) -- a 4x4 stride-1 pad-2 conv whose taps outside 0 <= ky <= 6 are zero.  Same products,
@@ -261,35 +230,6 @@ int add_stem_s2d(peanut_rcnn* h, const TensorMap& tm, const std::string& name, i
   return 0;
 }
 
-// conv3 + FrozenBN and the block's stride-1 shortcut conv + FrozenBN as one pointwise layer over [conv2 output | block
-// input] (detectron2 BottleneckBlock.forward: out = conv3(out) + shortcut(x), then ReLU): scales folded into the weights,
-// shifts added -- the same restatement as pred_api.hip: add_fused_c3d.
-int add_fused_c3s(peanut_rcnn* h, const TensorMap& tm, const std::string& blk, int bott, int cin, int cout, ConvLayer** out) {
-  int rc = 0;
-  const int64_t w3s[4] = {cout, bott, 1, 1}, wss[4] = {cout, cin, 1, 1};
-  const peanut_tensor* w3 = tm.get(blk + ".conv3.weight", 4, w3s, &rc);
-  if (!w3) return rc;
-  const peanut_tensor* ws = tm.get(blk + ".shortcut.weight", 4, wss, &rc);
-  if (!ws) return rc;
-  std::vector<float> s3(cout), b3(cout), ss(cout), bs(cout);
-  if ((rc = bn_fold_eps(tm, blk + ".conv3.norm", cout, h->cfg.bn_eps, s3.data(), b3.data()))) return rc;
-  if ((rc = bn_fold_eps(tm, blk + ".shortcut.norm", cout, h->cfg.bn_eps, ss.data(), bs.data()))) return rc;
-  const int k = bott + cin;
-  std::vector<float> w((size_t)cout * k), shift(cout);
-  for (int n = 0; n < cout; ++n) {
-    for (int c = 0; c < bott; ++c) w[(size_t)n * k + c] = s3[n] * w3->data[(size_t)n * bott + c];
-    for (int c = 0; c < cin; ++c) w[(size_t)n * k + bott + c] = ss[n] * ws->data[(size_t)n * cin + c];
-    shift[n] = b3[n] + bs[n];
-  }
-  auto L = std::make_unique<ConvLayer>();
-  L->name = blk + ".conv3+shortcut";
-  if ((rc = upload_conv(*L, w.data(), nullptr, shift.data(), cout, k, k, 1, 1, 1, 0, 1, 1,
-                        rs_planes_of(h->cfg.precision) ? h->cfg.precision : PEANUT_PREC_FP32))) return rc;
-  *out = L.get();
-  h->convs.push_back(std::move(L));
-  return 0;
-}
-
 void resized_hw(const peanut_rcnn_cfg& c, int h, int w, int* nh, int* nw) {
   // detectron2 ResizeShortestEdge.get_output_shape
   const double size = (double)c.min_size;
@@ -314,10 +254,9 @@ void push_rconv(RPlan& pl, Arena& ar, const ConvLayer* L, const Act& in, const A
   op.flops = conv_flops(L, out);
   op.ext_slot = ext_slot;
   if (L->has_wino) {
-    size_t vf, mf;
-    wino_scratch_floats(*L, in.B, in.H, in.W, &vf, &mf);
-    op.wino_v.bytes = vf * sizeof(float); op.wino_v.off = ar.alloc(op.wino_v.bytes);
-    op.wino_m.bytes = mf * sizeof(float); op.wino_m.off = ar.alloc(op.wino_m.bytes);
+    const WinoShape sh = wino_shape(*L, in.B, in.H, in.W);
+    op.wino_v.bytes = sh.v_floats * sizeof(float); op.wino_v.off = ar.alloc(op.wino_v.bytes);
+    op.wino_m.bytes = sh.m_floats * sizeof(float); op.wino_m.off = ar.alloc(op.wino_m.bytes);
     op.has_wino = true;
     if (keep) {                // (an op that runs next to later ones keeps its scratch until they have joined)
       keep->push_back(op.wino_v);
@@ -351,9 +290,8 @@ bool rconv_on_side(const RPlan& pl, const ROp& op) { return op.side && pl.splitk
 std::string rconv_family(const RPlan& pl, const ROp& op) {
   const ConvArgs a = rconv_args(pl, op, kPlanningBase, rconv_on_side(pl, op));
   if (!conv_layer_runs_wino(*op.conv, op.has_in2, op.has_wino)) return conv_kernel_family(conv_route(op.conv->d, a));
-  int gran;
-  long long m_pad;
-  const ConvArgs g = wino_gemm_args(*op.conv, a.B, a.H, a.W, nullptr, nullptr, a.ws, a.ws_floats, &gran, &m_pad);
+  // what launch_conv_layer launches (valid rows 0 there)
+  const ConvArgs g = wino_gemm_args(*op.conv, wino_shape(*op.conv, a.B, a.H, a.W).m_pad, 0, nullptr, nullptr, a.ws, a.ws_floats);
   return std::string("wino+") + conv_kernel_family(conv_route(op.conv->wino, g));
 }
 
@@ -403,8 +341,8 @@ std::unique_ptr<RPlan> build_rplan(const peanut_rcnn* h, int B, int H, int W) {
       {   // conv1's output is read by conv2 alone: conv2's input transform may sum conv1's split-K partial tiles (common.h: DeferredSplit)
         ROp& o2 = pl->ops[pl->ops.size() - 1];
         ROp& o1 = pl->ops[pl->ops.size() - 2];
-        if (opt(OPT_DEFER_SPLITK) != 0 && o2.has_wino && o1.conv == blk.c1 && !o1.has_res && o1.ext_slot < 0 &&
-            conv_layer_accepts_deferred(*o2.conv, t1.B, t1.H, t1.W))
+        if (opt(OPT_DEFER_SPLITK) != 0 && o2.has_wino && o1.conv == blk.c1 && !o1.has_res && o1.ext_slot < 0 && !o2.conv->d.rs &&
+            !o2.conv->wino.rs && wino_shape(*o2.conv, t1.B, t1.H, t1.W).accepts_deferred)
           o1.defer_ok = true;
       }
       rel(t1);
@@ -510,14 +448,7 @@ std::unique_ptr<RPlan> build_rplan(const peanut_rcnn* h, int B, int H, int W) {
   }
   for (ROp& op : pl->ops)
     if (op.kind == R_CONV) op.kernel = rconv_family(*pl, op);
-  size_t hw = pl->splitk.off + Arena::round_up(pl->splitk.bytes);
-  if (pl->rpn.on)
-    for (const Act* a : {&pl->rpn.v, &pl->rpn.m, &pl->rpn.t_all, &pl->rpn.obj_all, &pl->rpn.dl_all})
-      if (a->off + Arena::round_up(a->bytes) > hw) hw = a->off + Arena::round_up(a->bytes);
-  for (const auto& op : pl->ops)
-    for (const Act* a : {&op.in, &op.in2, &op.res, &op.out, &op.wino_v, &op.wino_m})
-      if (a->bytes && a->off + Arena::round_up(a->bytes) > hw) hw = a->off + Arena::round_up(a->bytes);
-  pl->bytes = hw;
+  pl->bytes = ar.high;
   return pl;
 }
 
@@ -557,7 +488,15 @@ int peanut_rcnn_create(peanut_rcnn_t** out, const peanut_rcnn_cfg* cfg, const pe
   for (int i = 0; i < n; ++i)
     if (tensors[i].name) tm.m[tensors[i].name] = &tensors[i];
   int rc;
-  if ((rc = add_rconv(h.get(), tm, "backbone.bottom_up.stem.conv1", 3, 16, cfg->stem_out, 7, 2, 3, true, 1, &h->stem))) return rc;
+  // fp32 kernels: the prediction planner's forms (F(6x6) with an F(4x4) twin, chosen per shape in push_rconv; the position
+  // GEMMs accumulate in two levels, net_common.h); emulated modes: F(4x4)
+  const LayerPolicy policy{cfg->bn_eps, cfg->precision, cfg->conv_algo, rs_planes_of(cfg->precision) ? 4 : rcnn_wino_request(), 128};
+  // detectron2 names a conv's FrozenBatchNorm <conv>.norm; a conv without one has a bias.  No dilation anywhere.
+  auto add_rconv = [&](const std::string& name, int cin, int cin_pad, int cout, int k, int stride, int pad,
+                       bool norm, int relu, ConvLayer** out) {
+    return add_conv_layer(h->convs, tm, policy, name, norm ? name + ".norm" : std::string(), cin, cin_pad, cout, k, stride, pad, 1, relu, out);
+  };
+  if ((rc = add_rconv("backbone.bottom_up.stem.conv1", 3, 16, cfg->stem_out, 7, 2, 3, true, 1, &h->stem))) return rc;
   const bool stem_s2d = opt(OPT_RCNN_STEM_S2D) != 0;
   if (stem_s2d && (rc = add_stem_s2d(h.get(), tm, "backbone.bottom_up.stem.conv1", cfg->stem_out, &h->stem_s2d))) return rc;
   const int nblocks[3][4] = {{3, 4, 6, 3}, {3, 4, 23, 3}, {3, 8, 36, 3}};
@@ -570,13 +509,14 @@ int peanut_rcnn_create(peanut_rcnn_t** out, const peanut_rcnn_cfg* cfg, const pe
       const int s = (bi == 0 && si > 0) ? 2 : 1;
       const int s1 = cfg->stride_in_1x1 ? s : 1, s3 = cfg->stride_in_1x1 ? 1 : s;
       peanut_rcnn::Block b{nullptr, nullptr, nullptr, nullptr, nullptr};
-      if (cin != cout && (rc = add_rconv(h.get(), tm, p + ".shortcut", cin, cin, cout, 1, s, 0, true, 0, &b.shortcut))) return rc;
-      if ((rc = add_rconv(h.get(), tm, p + ".conv1", cin, cin, bott, 1, s1, 0, true, 1, &b.c1))) return rc;
-      if ((rc = add_rconv(h.get(), tm, p + ".conv2", bott, bott, bott, 3, s3, 1, true, 1, &b.c2))) return rc;
-      if ((rc = add_rconv(h.get(), tm, p + ".conv3", bott, bott, cout, 1, 1, 0, true, 1, &b.c3))) return rc;   // ReLU after the add
+      if (cin != cout && (rc = add_rconv(p + ".shortcut", cin, cin, cout, 1, s, 0, true, 0, &b.shortcut))) return rc;
+      if ((rc = add_rconv(p + ".conv1", cin, cin, bott, 1, s1, 0, true, 1, &b.c1))) return rc;
+      if ((rc = add_rconv(p + ".conv2", bott, bott, bott, 3, s3, 1, true, 1, &b.c2))) return rc;
+      if ((rc = add_rconv(p + ".conv3", bott, bott, cout, 1, 1, 0, true, 1, &b.c3))) return rc;   // ReLU after the add
       // conv_algo AUTO only: DIRECT keeps detectron2's op-for-op form (conv3 -> FrozenBN, shortcut -> FrozenBN, add, ReLU)
       if (cfg->conv_algo == PEANUT_ALGO_AUTO && b.shortcut && s == 1 && bott % 32 == 0 && cin % 32 == 0 && conv_pw_enabled() &&
-          (rc = add_fused_c3s(h.get(), tm, p, bott, cin, cout, &b.c3s)))
+          (rc = add_fused_pair_layer(h->convs, tm, policy, p + ".conv3+shortcut", p + ".conv3", p + ".conv3.norm", p + ".shortcut", p + ".shortcut.norm",
+                                     bott, cin, cout, &b.c3s)))
         return rc;
       blocks.push_back(b);
       cin = cout;
@@ -588,13 +528,13 @@ int peanut_rcnn_create(peanut_rcnn_t** out, const peanut_rcnn_cfg* cfg, const pe
   int c = cfg->res2_out;
   for (int lvl = 0; lvl < 4; ++lvl, c *= 2) {
     const std::string l = std::to_string(lvl + 2);
-    if ((rc = add_rconv(h.get(), tm, "backbone.fpn_lateral" + l, c, c, cfg->fpn_out, 1, 1, 0, false, 0, &h->lateral[lvl]))) return rc;
-    if ((rc = add_rconv(h.get(), tm, "backbone.fpn_output" + l, cfg->fpn_out, cfg->fpn_out, cfg->fpn_out, 3, 1, 1, false, 0, &h->output[lvl]))) return rc;
+    if ((rc = add_rconv("backbone.fpn_lateral" + l, c, c, cfg->fpn_out, 1, 1, 0, false, 0, &h->lateral[lvl]))) return rc;
+    if ((rc = add_rconv("backbone.fpn_output" + l, cfg->fpn_out, cfg->fpn_out, cfg->fpn_out, 3, 1, 1, false, 0, &h->output[lvl]))) return rc;
   }
   const int f = cfg->fpn_out;
-  if ((rc = add_rconv(h.get(), tm, "proposal_generator.rpn_head.conv", f, f, f, 3, 1, 1, false, 1, &h->rpn_conv))) return rc;
-  if ((rc = add_rconv(h.get(), tm, "proposal_generator.rpn_head.objectness_logits", f, f, cfg->num_anchors, 1, 1, 0, false, 0, &h->rpn_obj))) return rc;
-  if ((rc = add_rconv(h.get(), tm, "proposal_generator.rpn_head.anchor_deltas", f, f, cfg->num_anchors * 4, 1, 1, 0, false, 0, &h->rpn_delta))) return rc;
+  if ((rc = add_rconv("proposal_generator.rpn_head.conv", f, f, f, 3, 1, 1, false, 1, &h->rpn_conv))) return rc;
+  if ((rc = add_rconv("proposal_generator.rpn_head.objectness_logits", f, f, cfg->num_anchors, 1, 1, 0, false, 0, &h->rpn_obj))) return rc;
+  if ((rc = add_rconv("proposal_generator.rpn_head.anchor_deltas", f, f, cfg->num_anchors * 4, 1, 1, 0, false, 0, &h->rpn_delta))) return rc;
   if (tm.m.count("roi_heads.box_head.fc1.weight") && (rc = peanut_rcnn_build_heads(h.get(), tm))) return rc;
   PEANUT_HIP_CHECK(hipDeviceSynchronize());
   *out = h.release();
@@ -674,19 +614,14 @@ static int rcnn_front_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int 
   if (events) PEANUT_HIP_CHECK(hipEventRecord(events[0], s));
   // side stream of the FPN output convs (not while probing: the per-op events time one stream)
   const bool use_side = !events && pl->splitk_side.bytes != 0;
-  if (use_side && !h->side) {
-    PEANUT_HIP_CHECK(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-    PEANUT_HIP_CHECK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    PEANUT_HIP_CHECK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  }
+  if (use_side && (rc = h->side.ensure())) return rc;
   bool side_pending = false;
   size_t op_index = 0;
   DeferredSplit deferred{};        // handed from a conv1 that skipped its split-K reduce to the conv2 right behind it
   for (const auto& op : pl->ops) {
     const bool skip = (op.kind == R_RPN_FUSED && !rpn_fused) || (op.rpn_level && rpn_fused);
     if (op.join_side && side_pending) {
-      PEANUT_HIP_CHECK(hipEventRecord(h->ev_join, h->side));
-      PEANUT_HIP_CHECK(hipStreamWaitEvent(s, h->ev_join, 0));
+      if ((rc = h->side.join(s))) return rc;
       side_pending = false;
     }
     if (skip) {
@@ -708,12 +643,8 @@ static int rcnn_front_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int 
           if ((rc = launch_wino_input(xin, V + (size_t)f.tile_off[l] * cin, B, f.in[l].H, f.in[l].W, cin, 1, s, f.gran, L.wino_m, f.m_pad_total)))
             return rc;
         }
-        ConvArgs g{};
-        g.x = V; g.y = M;
-        g.B = 1; g.H = 1; g.W = (int)((long long)L.wino_np() * f.m_pad_total); g.c1 = cin; g.c2 = 0; g.Ho = 1; g.Wo = g.W;
-        g.ws = P(pl->splitk); g.ws_floats = kSplitKScratchFloats;
-        g.mt_per_group = (int)(f.m_pad_total / 128); g.w_group_stride = L.wino.rs ? L.wino_group_bytes : L.wino_group_floats;
-        if ((rc = launch_conv(L.wino, g, s))) return rc;
+        // all levels' tiles in every position's rows (valid rows 0: as launch_conv_layer, inherited and not a decision)
+        if ((rc = launch_conv(L.wino, wino_gemm_args(L, f.m_pad_total, 0, V, M, P(pl->splitk), kSplitKScratchFloats), s))) return rc;
         for (int l = 0; l < 5; ++l)
           if ((rc = launch_wino_output(M + (size_t)f.tile_off[l] * cout, L.d.scale, L.d.shift, nullptr, T + (size_t)f.row_off[l] * cout, B,
                                        f.in[l].H, f.in[l].W, cout, 1, L.d.relu, s, f.gran, L.wino_m, f.m_pad_total)))
@@ -748,9 +679,8 @@ static int rcnn_front_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, int 
         a.y = OUT(op);
         hipStream_t os = s;
         if (on_side) {      // behind everything enqueued so far, next to what follows
-          PEANUT_HIP_CHECK(hipEventRecord(h->ev_fork, s));
-          PEANUT_HIP_CHECK(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-          os = h->side;
+          if ((rc = h->side.fork(s))) return rc;
+          os = h->side.stream;
           side_pending = true;
         }
         DeferredSplit* produced = deferred.valid ? &deferred : nullptr;     // (the previous op's, consumed by this one)

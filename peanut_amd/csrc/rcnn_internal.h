@@ -72,13 +72,7 @@ struct peanut_rcnn {
   struct PostBufs;                       // scratch of peanut_rcnn_inference (rcnn_post.hip)
   std::shared_ptr<PostBufs> post;
   // FPN side stream (rcnn_api.hip): the output convs of p5, p4, p3 next to the lateral / top-down chain that ends in p2's
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  ~peanut_rcnn() {
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    if (side) (void)hipStreamDestroy(side);
-  }
+  peanut::SideStream side;
 };
 
 

@@ -1316,7 +1316,7 @@ static int rcnn_inference_impl(peanut_rcnn_t* h, const uint8_t* img_bgr, int B, 
   const int Pm = c.mask_pooler_resolution, mc = c.mask_conv_dim;
   size_t vf = 0, mf = 0;
   for (const ConvLayer* L : h->mask_fcn)
-    if (L->has_wino) { size_t v, m; wino_scratch_floats(*L, n, Pm, Pm, &v, &m); vf = std::max(vf, v); mf = std::max(mf, m); }
+    if (L->has_wino) { const WinoShape sh = wino_shape(*L, n, Pm, Pm); vf = std::max(vf, sh.v_floats); mf = std::max(mf, sh.m_floats); }
   const size_t act = (size_t)n * Pm * Pm * std::max(F, mc) * 4;
   if ((rc = pb.mrois.ensure((size_t)n * 20)) || (rc = pb.mlevel.ensure((size_t)n * 4)) || (rc = pb.mx0.ensure(act)) || (rc = pb.mx1.ensure(act)) ||
       (rc = pb.mdeconv.ensure((size_t)n * Pm * Pm * 4 * mc * 4)) || (rc = pb.mlogits.ensure((size_t)n * Pm * Pm * 4 * K * 4)) ||
