@@ -181,6 +181,59 @@ size_t peanut_pred_workspace_bytes(peanut_pred_t* h, int B, int H, int W);
 /* Conv FLOPs (2 x MACs over the 61 convolutions) of one HxW map. */
 double peanut_pred_flops_per_map(peanut_pred_t* h, int H, int W);
 
+/* Sliding-window and flip-averaged inference (ABI 24; csrc/pred_infer.hip): what the reference's EncoderDecoder does around its
+ * forward when nav/pred_model_cfg.py says test_cfg.mode='slide' or the test pipeline's MultiScaleFlipAug says flip=True --
+ * slide_inference (prediction/mmseg/models/segmentors/encoder_decoder.py:155-201), the flip branch of inference() (:249-256) and
+ * the averaging of aug_test (:273-291), reached through BaseSegmentor.forward_test (segmentors/base.py:62-110) with the images
+ * MultiScaleFlipAug builds (datasets/pipelines/test_time_aug.py:102-135).  Arguments as a descriptor; the stream the work is
+ * enqueued on travels in it (NULL = default stream).
+ *   Window grid (:166-177, per axis): grids = max(n - crop + stride - 1, 0) / stride + 1; window i ends at min(i * stride + crop, n)
+ * and starts at max(end - crop, 0): a ragged last window is shifted back, and a crop larger than the image gives the one window
+ * min(crop, n) ("the small patch will be used").  Whole mode is the one window (0, 0, H, W).
+ *   Three steps: ONE launch gathers every window of every flipped image into a staged batch [N, C, ch, cw], N = n_augs * B * windows,
+ * ordered aug-major, then sample, then window row-major (the flip is applied to the whole image before the windows are cut, as the
+ * pipeline's np.flip does); the forward of peanut_pred_forward -- raw logits at window resolution, never the hipGraph replay -- runs
+ * over the staged batch in chunks of max_batch maps; ONE launch combines.  The rule of the combine, held bit for bit:
+ *     per aug a:  s = +0.0f;  s = s + logit for every window that covers the pixel, in row-major window order;
+ *                 slide: p_a = s / (float)count (an IEEE division);  whole: p_a = the logit;  p_a is then un-flipped;
+ *     out = p_0;  out = out + p_a for a = 1.. in order;  if n_augs > 1: out = out / (float)n_augs (simple_test does not divide);
+ *     then the optional sigmoid (apply_sigmoid = 1).
+ * The final resize of :195-200 / :216-221 is at ratio 1.0 (img_ratios other than [1.0] are refused by the config reader) and is the
+ * identity: it is not launched.  The last bits of a logit depend on the batch size of its forward (see "Conv arithmetic" below),
+ * hence on max_batch.  in_dev: [B, in_channels, H, W] NCHW fp32; out_dev: [B, num_classes, H, W], written whole.  The staging
+ * buffers are allocated on first use and cached on the handle, like the activation workspace (growing them frees the old ones).
+ * No synchronisation: the window grid is host arithmetic and nothing is read back.  PEANUT_EINVAL with nothing enqueued: a null
+ * pointer, B < 1, a mode other than 0 / 1, slide mode with a crop or stride below 1, a pixel that no window covers (stride > crop:
+ * the reference asserts on it), more than PEANUT_INFER_MAX_GRID windows on an axis, an effective window below the forward's
+ * minimum of 16, n_augs outside 1..PEANUT_INFER_MAX_AUGS, a flip code outside 0..2, max_batch < 0, out_dev overlapping in_dev, a
+ * handle under the event probe. */
+#define PEANUT_INFER_MAX_AUGS 4
+#define PEANUT_INFER_MAX_GRID 32           /* windows per axis */
+typedef struct {
+  int mode;                                /* 0 whole, 1 slide */
+  int crop_h, crop_w, stride_h, stride_w;  /* slide: test_cfg.crop_size / .stride, (h, w) */
+  int n_augs;                              /* 1 .. 4: the images forward_test is handed */
+  int flip[PEANUT_INFER_MAX_AUGS];         /* per aug: 0 none, 1 horizontal (dims=(3,)), 2 vertical (dims=(2,)) */
+  int max_batch;                           /* most maps per internal forward; 0 = all of them in one */
+  void* stream;
+} peanut_pred_infer_t;
+int peanut_pred_inference(peanut_pred_t* h, const peanut_pred_infer_t* infer, const float* in_dev, float* out_dev,
+                          int B, int H, int W, int apply_sigmoid);
+/* The window grid of a descriptor on an H x W image, host only: y1 / x1 (each int[PEANUT_INFER_MAX_GRID], may be NULL) receive the
+ * per-axis window starts (the grid is separable; entries past the axis' count are -1), *ch / *cw the effective window size
+ * min(crop, n).  Returns h_grids * w_grids, or PEANUT_EINVAL for everything peanut_pred_inference refuses that needs no handle. */
+int peanut_pred_infer_windows(const peanut_pred_infer_t* infer, int H, int W, int* y1, int* x1, int* ch, int* cw);
+/* Bytes the call needs on the handle: the two staging buffers and the activation workspace of its largest forward (0 on error). */
+size_t peanut_pred_inference_workspace_bytes(peanut_pred_t* h, const peanut_pred_infer_t* infer, int B, int H, int W);
+/* The two glue launches of peanut_pred_inference on the caller's buffers, no handle (tests and tools/bench_infer.py time them alone;
+ * a caller with a forward of its own can put it between them).  Gather: in_dev [B, C, H, W] -> staged_dev [N, C, ch, cw] in the
+ * order above.  Combine: logits_dev [N, K, ch, cw] in that order -> out_dev [B, K, H, W] by the rule above.  One launch each on
+ * infer->stream.  No synchronisation, no allocation.  PEANUT_EINVAL with nothing enqueued: as peanut_pred_infer_windows; a null
+ * pointer; B, C or K below 1; source and destination overlapping. */
+int peanut_pred_infer_gather(const peanut_pred_infer_t* infer, const float* in_dev, float* staged_dev, int B, int C, int H, int W);
+int peanut_pred_infer_combine(const peanut_pred_infer_t* infer, const float* logits_dev, float* out_dev, int B, int K, int H, int W,
+                              int apply_sigmoid);
+
 /* Test/bisect hook: keep every intermediate of subsequent forwards in its own buffer
  * (keep=1) and fetch one by name after a forward.  Names: "stem0","stem1","stem2","pool",
  * "layer1".."layer4","ppm_table","bottleneck","logits_lowres".  *dev_out points into the

@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 23   # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 24   # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -139,6 +139,17 @@ class VisEpisodeC(C.Structure):
                 ("index_map", C.c_void_p), ("ranges", C.c_void_p), ("frame", C.c_void_p)]
 
 
+INFER_MAX_AUGS = 4         # PEANUT_INFER_MAX_AUGS
+INFER_MAX_GRID = 32        # PEANUT_INFER_MAX_GRID
+
+
+class PredInferC(C.Structure):
+    """peanut_pred_infer_t: test_cfg (mode, crop_size, stride), the flips of the images forward_test is handed, the chunk size of the
+    internal forwards and the stream the call is enqueued on."""
+    _fields_ = [("mode", C.c_int), ("crop_h", C.c_int), ("crop_w", C.c_int), ("stride_h", C.c_int), ("stride_w", C.c_int),
+                ("n_augs", C.c_int), ("flip", C.c_int * INFER_MAX_AUGS), ("max_batch", C.c_int), ("stream", C.c_void_p)]
+
+
 MAPSEQ_MAX_BATCH = 16      # PEANUT_MAPSEQ_MAX_BATCH
 MAPSEQ_MAX_SAMPLES = 64    # PEANUT_MAPSEQ_MAX_SAMPLES
 
@@ -164,6 +175,12 @@ SIGNATURES = {
     "peanut_pred_destroy": (None, [_P]),
     "peanut_pred_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "peanut_pred_workspace_bytes": (C.c_size_t, [_P, C.c_int, C.c_int, C.c_int]),
+    "peanut_pred_inference": (C.c_int, [_P, C.POINTER(PredInferC), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "peanut_pred_infer_windows": (C.c_int, [C.POINTER(PredInferC), C.c_int, C.c_int, C.POINTER(C.c_int * INFER_MAX_GRID),
+                                            C.POINTER(C.c_int * INFER_MAX_GRID), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "peanut_pred_inference_workspace_bytes": (C.c_size_t, [_P, C.POINTER(PredInferC), C.c_int, C.c_int, C.c_int]),
+    "peanut_pred_infer_gather": (C.c_int, [C.POINTER(PredInferC), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "peanut_pred_infer_combine": (C.c_int, [C.POINTER(PredInferC), _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "peanut_pred_flops_per_map": (C.c_double, [_P, C.c_int, C.c_int]),
     "peanut_pred_debug_keep": (C.c_int, [_P, C.c_int]),
     "peanut_pred_debug_tensor": (C.c_int, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_int * 4)]),

@@ -248,4 +248,17 @@ int launch_ppm_conv_term(const float* Q, float* R, int B, int H, int W, int C, c
 int launch_upsample_logits(const float* lo, float* out, int B, int h, int w, int K, int H, int W,
                            int align_corners, int sigmoid, hipStream_t s);
 
+// ---- sliding-window / flip-averaged inference (pred_infer.hip) ----
+// The validated window grid of a peanut_pred_infer_t on an H x W image: ny x nx windows of ch x cw, starts per axis.
+struct InferGrid {
+  int ny, nx, ch, cw;
+  int y1[32], x1[32];      // PEANUT_INFER_MAX_GRID
+};
+// staged[n][c][r][j] = flip_a(in[b])[c][y1[wy] + r][x1[wx] + j], n = (a * B + b) * ny * nx + wy * nx + wx
+int launch_infer_gather(const float* in, float* staged, const InferGrid& g, int n_augs, const int* flip, int B, int C, int H, int W,
+                        hipStream_t s);
+// out [B,K,H,W] from the staged logits [n][K][ch][cw]: window mean (slide), un-flip, aug mean, optional sigmoid
+int launch_infer_combine(const float* logits, float* out, const InferGrid& g, int slide, int n_augs, const int* flip, int B, int K,
+                         int H, int W, int sigmoid, hipStream_t s);
+
 }  // namespace peanut

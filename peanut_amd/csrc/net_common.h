@@ -641,4 +641,7 @@ struct SideStream {
   }
 };
 
+// pred_infer.hip: every check of a peanut_pred_infer_t that needs no handle, and its window grid (host arithmetic)
+int infer_grid(const peanut_pred_infer_t* d, int H, int W, InferGrid* g, const char* who);
+
 }  // namespace peanut

@@ -10,6 +10,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <string>
@@ -110,6 +111,7 @@ struct peanut_pred {
   std::vector<std::vector<hipEvent_t>> probe_events;  // one vector (n_ops + 1 events) per forward
   std::vector<hipEvent_t> event_pool;
   SideStream side;   // of the two-stream PSP-head schedule (created on first use)
+  DevBuf infer_in, infer_out;   // peanut_pred_inference: the staged windows [N, C, ch, cw] and their logits [N, K, ch, cw], grown on demand
   ~peanut_pred() {
     for (auto& v : probe_events) for (auto e : v) (void)hipEventDestroy(e);
     for (auto e : event_pool) (void)hipEventDestroy(e);
@@ -526,7 +528,7 @@ extern "C" {
 
 const char* peanut_last_error(void) { return g_err.c_str(); }
 const char* peanut_last_conv_kernel(void) { return noted_kernel(); }
-int peanut_abi_version(void) { return 23; }
+int peanut_abi_version(void) { return 24; }
 const char* peanut_build_arch(void) { return "gfx950"; }
 #ifndef PEANUT_SOURCE_HASH
 #define PEANUT_SOURCE_HASH ""
@@ -755,9 +757,10 @@ int peanut_pred_debug_read(peanut_pred_t* h, const char* name, float* dst_dev, s
   return 0;
 }
 
-int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, int B, int H, int W, int apply_sigmoid,
-                        void* stream) {
-  if (!h || !in_dev || !out_dev) return fail(PEANUT_EINVAL, "peanut_pred_forward: null argument");
+// The forward behind peanut_pred_forward and peanut_pred_inference.  may_replay: the launch sequence may go through the handle's
+// hipGraph cache (peanut_pred_use_graph); the inference path always enqueues its forwards plainly.
+static int pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, int B, int H, int W, int apply_sigmoid,
+                        void* stream, bool may_replay) {
   OptionScope option_scope(&h->opts);
   Plan* pl = get_plan(h, B, H, W);
   if (!pl) return PEANUT_EINVAL;
@@ -779,7 +782,7 @@ int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, i
       }
       return 0;
     };
-    if (!h->use_graph || h->keep_all) return enqueue();
+    if (!may_replay || !h->use_graph || h->keep_all) return enqueue();
     return h->graphs.run({(uintptr_t)pl, (uintptr_t)in_dev, (uintptr_t)out_dev, (uintptr_t)apply_sigmoid, (uintptr_t)s}, s, enqueue);
   }
   if (h->probe_plan && h->probe_plan != pl) return fail(PEANUT_EINVAL, "probe: shape changed while probing; collect first");
@@ -800,6 +803,68 @@ int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, i
   }
   h->probe_events.push_back(std::move(ev));
   return 0;
+}
+
+int peanut_pred_forward(peanut_pred_t* h, const float* in_dev, float* out_dev, int B, int H, int W, int apply_sigmoid,
+                        void* stream) {
+  if (!h || !in_dev || !out_dev) return fail(PEANUT_EINVAL, "peanut_pred_forward: null argument");
+  return pred_forward(h, in_dev, out_dev, B, H, W, apply_sigmoid, stream, true);
+}
+
+// ---- sliding-window / flip-averaged inference (kernels and window grid: pred_infer.hip) ----
+namespace {
+// staged maps of a call and the most that one internal forward takes
+struct InferSizes { long long N; int chunk; };
+int infer_sizes(const peanut_pred_infer_t* d, const InferGrid& g, int B, InferSizes* z, const char* who) {
+  if (B < 1) return fail(PEANUT_EINVAL, std::string(who) + ": B must be >= 1");
+  z->N = (long long)d->n_augs * B * g.ny * g.nx;
+  if (z->N > (1 << 20)) return fail(PEANUT_EINVAL, std::string(who) + ": more than 2^20 staged windows");
+  z->chunk = (int)(d->max_batch > 0 ? std::min<long long>(d->max_batch, z->N) : z->N);
+  return 0;
+}
+}  // namespace
+
+size_t peanut_pred_inference_workspace_bytes(peanut_pred_t* h, const peanut_pred_infer_t* infer, int B, int H, int W) {
+  InferGrid g;
+  InferSizes z;
+  if (!h || infer_grid(infer, H, W, &g, "peanut_pred_inference_workspace_bytes") ||
+      infer_sizes(infer, g, B, &z, "peanut_pred_inference_workspace_bytes"))
+    return 0;
+  OptionScope option_scope(&h->opts);
+  Plan* pl = get_plan(h, z.chunk, g.ch, g.cw);
+  if (!pl) return 0;
+  return pl->bytes + (size_t)z.N * (h->cfg.in_channels + h->cfg.num_classes) * g.ch * g.cw * sizeof(float);
+}
+
+int peanut_pred_inference(peanut_pred_t* h, const peanut_pred_infer_t* infer, const float* in_dev, float* out_dev, int B, int H, int W,
+                          int apply_sigmoid) {
+  const char* who = "peanut_pred_inference";
+  if (!h || !infer || !in_dev || !out_dev) return fail(PEANUT_EINVAL, "peanut_pred_inference: null argument");
+  InferGrid g;
+  InferSizes z;
+  int rc;
+  if ((rc = infer_grid(infer, H, W, &g, who)) || (rc = infer_sizes(infer, g, B, &z, who))) return rc;
+  const int C = h->cfg.in_channels, K = h->cfg.num_classes;
+  const size_t plane = (size_t)H * W * sizeof(float);
+  const uintptr_t in0 = (uintptr_t)in_dev, in1 = in0 + (size_t)B * C * plane, out0 = (uintptr_t)out_dev, out1 = out0 + (size_t)B * K * plane;
+  if (in0 < out1 && out0 < in1) return fail(PEANUT_EINVAL, "peanut_pred_inference: out_dev overlaps in_dev");
+  if (h->probe) return fail(PEANUT_EINVAL, "peanut_pred_inference: not under the event probe (it times one plan; use peanut_pred_forward)");
+  OptionScope option_scope(&h->opts);       // the plans' policy, and debug_poison_alloc for the staging buffers
+  {   // every forward's plan exists before anything is enqueued: a shape the forward refuses is refused here
+    const int last = (int)(z.N % z.chunk);
+    if (!get_plan(h, z.chunk, g.ch, g.cw) || (last && !get_plan(h, last, g.ch, g.cw))) return PEANUT_EINVAL;
+  }
+  const size_t win = (size_t)g.ch * g.cw;
+  if ((rc = h->infer_in.ensure((size_t)z.N * C * win * sizeof(float))) || (rc = h->infer_out.ensure((size_t)z.N * K * win * sizeof(float)))) return rc;
+  float* staged = (float*)h->infer_in.p;
+  float* logits = (float*)h->infer_out.p;
+  hipStream_t s = (hipStream_t)infer->stream;
+  if ((rc = launch_infer_gather(in_dev, staged, g, infer->n_augs, infer->flip, B, C, H, W, s))) return rc;
+  for (long long n = 0; n < z.N; n += z.chunk) {
+    const int nb = (int)std::min<long long>(z.chunk, z.N - n);
+    if ((rc = pred_forward(h, staged + (size_t)n * C * win, logits + (size_t)n * K * win, nb, g.ch, g.cw, 0, infer->stream, false))) return rc;
+  }
+  return launch_infer_combine(logits, out_dev, g, infer->mode, infer->n_augs, infer->flip, B, K, H, W, apply_sigmoid, s);
 }
 
 int peanut_pred_use_graph(peanut_pred_t* h, int enable) {

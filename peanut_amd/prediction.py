@@ -25,6 +25,88 @@ def sigmoid(x):
     return 1.0 / (1.0 + np.exp(-np.asarray(x, dtype=np.float32)))
 
 
+def infer_descriptor(test_mode="whole", crop_size=None, stride=None, flips=(0,), max_batch: int = 0, stream: int = 0):
+    """A ``peanut_pred_infer_t``: ``test_cfg`` (mode, crop_size and stride as (h, w)), one flip code per image (0 none, 1 horizontal,
+    2 vertical), the chunk size of the internal forwards, the raw stream."""
+    if test_mode not in ("whole", "slide"):
+        raise ValueError(f"test_mode must be 'whole' or 'slide', got {test_mode!r}")
+    d = _lib.PredInferC()
+    d.mode = int(test_mode == "slide")
+    if d.mode:
+        if crop_size is None or stride is None:
+            raise ValueError("test_mode='slide' needs crop_size and stride")
+        (d.crop_h, d.crop_w), (d.stride_h, d.stride_w) = crop_size, stride
+    d.n_augs = len(flips)
+    for i, f in enumerate(flips[:_lib.INFER_MAX_AUGS]):
+        d.flip[i] = int(f)
+    d.max_batch = int(max_batch)
+    d.stream = stream or None
+    return d
+
+
+def slide_windows(H: int, W: int, crop, stride):
+    """The window grid of ``slide_inference`` (``encoder_decoder.py:166-177``) on an H x W image, from the library
+    (``peanut_pred_infer_windows``: host arithmetic, no device needed): ``(ys, xs, ch, cw)`` -- the window starts per axis and the
+    effective window size ``min(crop, image)``; window (i, j) is rows ``ys[i]:ys[i]+ch``, columns ``xs[j]:xs[j]+cw``.  Raises
+    ``PeanutHipError`` for a grid the library refuses (an uncovered pixel, more than 32 windows on an axis, a window below 16)."""
+    d = infer_descriptor("slide", crop, stride)
+    ys, xs = (C.c_int * _lib.INFER_MAX_GRID)(), (C.c_int * _lib.INFER_MAX_GRID)()
+    ch, cw = C.c_int(), C.c_int()
+    n = _lib.load().peanut_pred_infer_windows(C.byref(d), int(H), int(W), C.byref(ys), C.byref(xs), C.byref(ch), C.byref(cw))
+    if n < 0:
+        _lib.check(n, "peanut_pred_infer_windows")
+    ys, xs = [v for v in ys if v >= 0], [v for v in xs if v >= 0]
+    assert len(ys) * len(xs) == n
+    return ys, xs, ch.value, cw.value
+
+
+def _with_stream(d, device):
+    d.stream = _lib.current_stream_ptr(device) or None
+    return d
+
+
+def infer_gather(x: torch.Tensor, d) -> torch.Tensor:
+    """The gather launch alone (``peanut_pred_infer_gather``): float32 [B,C,H,W] on the device -> the staged batch [N,C,ch,cw] of
+    descriptor ``d`` (aug-major, then sample, then window row-major), enqueued on torch's current stream."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError("input must be a float32 [B,C,H,W] tensor on the HIP device")
+    b, c, h, w = x.shape
+    n = _lib.load().peanut_pred_infer_windows(C.byref(d), h, w, None, None, None, None)
+    if n < 0:
+        _lib.check(n, "peanut_pred_infer_windows")
+    ch, cw = (min(d.crop_h, h), min(d.crop_w, w)) if d.mode else (h, w)
+    x = x.contiguous()
+    out = torch.empty((d.n_augs * b * n, c, ch, cw), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().peanut_pred_infer_gather(C.byref(_with_stream(d, x.device)), x.data_ptr(), out.data_ptr(), b, c, h, w)
+    _lib.check(rc, "peanut_pred_infer_gather")
+    return out
+
+
+def infer_combine(logits: torch.Tensor, d, B: int, H: int, W: int, apply_sigmoid: bool = False,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The combine launch alone (``peanut_pred_infer_combine``): the staged logits [N,K,ch,cw] of descriptor ``d`` -> [B,K,H,W]."""
+    n = _lib.load().peanut_pred_infer_windows(C.byref(d), H, W, None, None, None, None)
+    if n < 0:
+        _lib.check(n, "peanut_pred_infer_windows")
+    ch, cw = (min(d.crop_h, H), min(d.crop_w, W)) if d.mode else (H, W)
+    if logits.dim() != 4 or (logits.shape[0], logits.shape[2], logits.shape[3]) != (d.n_augs * B * n, ch, cw):
+        raise ValueError(f"expected staged logits [{d.n_augs * B * n},K,{ch},{cw}], got {tuple(logits.shape)}")
+    if logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError("logits must be a float32 tensor on the HIP device")
+    logits = logits.contiguous()
+    k = logits.shape[1]
+    if out is not None and (tuple(out.shape) != (B, k, H, W) or not out.is_contiguous() or out.dtype != torch.float32):
+        raise ValueError("out has the wrong shape or dtype, or is not contiguous")
+    if out is None:
+        out = torch.empty((B, k, H, W), dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        rc = _lib.load().peanut_pred_infer_combine(C.byref(_with_stream(d, logits.device)), logits.data_ptr(), out.data_ptr(), B, k, H, W,
+                                                   int(apply_sigmoid))
+    _lib.check(rc, "peanut_pred_infer_combine")
+    return out
+
+
 class HipSegmentor:
     """What ``init_segmentor`` returns in the reference (an eval-mode EncoderDecoder on a CUDA
     device, ``prediction/mmseg/apis/inference.py:12-40``), here a handle of the HIP library."""
@@ -118,6 +200,48 @@ class HipSegmentor:
                                                int(apply_sigmoid), _lib.current_stream_ptr(x.device))
         _lib.check(rc, "peanut_pred_forward")
         return out
+
+    def infer_descriptor(self, max_batch: int = 0, stream: int = 0) -> "_lib.PredInferC":
+        """``peanut_pred_infer_t`` of this model's cfg (``test_mode``, ``crop_size``, ``stride``, ``augs``)."""
+        return infer_descriptor(self.cfg.test_mode, self.cfg.crop_size, self.cfg.stride, self.cfg.flip_codes, max_batch, stream)
+
+    def inference(self, x: torch.Tensor, apply_sigmoid: bool = False, out: Optional[torch.Tensor] = None,
+                  max_batch: int = 0) -> torch.Tensor:
+        """``EncoderDecoder.inference`` / ``aug_test`` under this model's cfg (``encoder_decoder.py:155-201,249-256,273-291``):
+        the sliding windows of ``test_mode='slide'`` and the flipped images of ``augs`` go through ONE batched forward (in chunks
+        of ``max_batch`` maps; 0 = all at once) between a gather and a combine launch (``peanut_pred_inference``).  x: the
+        UNFLIPPED float32 [B,C,H,W] maps on ``self.device`` -> [B, num_classes, H, W], enqueued on torch's current stream (no
+        synchronisation)."""
+        if x.dim() != 4 or x.shape[1] != self.cfg.in_channels:
+            raise ValueError(f"expected [B,{self.cfg.in_channels},H,W], got {tuple(x.shape)}")
+        if x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError("input must be a float32 tensor on the HIP device")
+        x = x.contiguous()
+        b, _, h, w = x.shape
+        if out is None:
+            out = torch.empty((b, self.cfg.num_classes, h, w), dtype=torch.float32, device=x.device)
+        elif tuple(out.shape) != (b, self.cfg.num_classes, h, w) or not out.is_contiguous():
+            raise ValueError("out has the wrong shape or is not contiguous")
+        with torch.cuda.device(x.device):
+            d = self.infer_descriptor(max_batch, _lib.current_stream_ptr(x.device))
+            rc = self._lib.peanut_pred_inference(self._h, C.byref(d), x.data_ptr(), out.data_ptr(), b, h, w, int(apply_sigmoid))
+        _lib.check(rc, "peanut_pred_inference")
+        return out
+
+    def predict(self, x: torch.Tensor, apply_sigmoid: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What the reference's model call returns for ``x`` under this cfg: ``forward_logits`` for whole_inference of one unflipped
+        image (the stock config), else ``inference``."""
+        if self.cfg.plain_inference:
+            return self.forward_logits(x, apply_sigmoid=apply_sigmoid, out=out)
+        return self.inference(x, apply_sigmoid=apply_sigmoid, out=out)
+
+    def inference_workspace_bytes(self, b: int, h: int, w: int, max_batch: int = 0) -> int:
+        d = self.infer_descriptor(max_batch)
+        return int(self._lib.peanut_pred_inference_workspace_bytes(self._h, C.byref(d), b, h, w))
+
+    @staticmethod
+    def slide_windows(H: int, W: int, crop, stride):
+        return slide_windows(H, W, crop, stride)
 
     def check_range(self, y: torch.Tensor) -> torch.Tensor:
         """fp16x3 only: an activation outside fp16's exponent range turns the output into NaN (include/peanut_hip.h);
@@ -220,7 +344,7 @@ def run_inference(model: HipSegmentor, full_map: np.ndarray) -> List[np.ndarray]
     if full_map.ndim != 3:
         raise ValueError(f"full_map must be [C,H,W], got shape {full_map.shape}")
     x = torch.from_numpy(np.ascontiguousarray(full_map, dtype=np.float32))[None].to(model.device)
-    y = model.check_range(model.forward_logits(x, apply_sigmoid=False))
+    y = model.check_range(model.predict(x, apply_sigmoid=False))   # slide / flip configs: inference(); aug_test returns the same list
     return list(y.cpu().numpy())               # .cpu() synchronises, like simple_test's
 
 
@@ -266,7 +390,7 @@ class PEANUT_Prediction_Model():
 
     def _checked_forward(self, x, apply_sigmoid, out):
         try:
-            return self.model.check_range(self.model.forward_logits(x, apply_sigmoid=apply_sigmoid, out=out))
+            return self.model.check_range(self.model.predict(x, apply_sigmoid=apply_sigmoid, out=out))
         except FloatingPointError:
             if self._escalate is None:
                 raise
@@ -277,7 +401,7 @@ class PEANUT_Prediction_Model():
             self.model = init_segmentor(cfg, **kw)
             self.model.eval()
             self.model.cfg = cfg
-            return self.model.forward_logits(x, apply_sigmoid=apply_sigmoid, out=out)
+            return self.model.predict(x, apply_sigmoid=apply_sigmoid, out=out)
 
     def get_prediction_batch(self, maps: torch.Tensor, apply_sigmoid: bool = True,
                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -286,4 +410,4 @@ class PEANUT_Prediction_Model():
         to bf16x6 -- the result is range-checked, which synchronises; every explicit precision stays asynchronous."""
         if self._escalate is not None:
             return self._checked_forward(maps, apply_sigmoid, out)
-        return self.model.forward_logits(maps, apply_sigmoid=apply_sigmoid, out=out)
+        return self.model.predict(maps, apply_sigmoid=apply_sigmoid, out=out)

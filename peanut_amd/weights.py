@@ -18,7 +18,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Dict, Iterable, List, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -40,10 +40,73 @@ class PredCfg:
     head_channels: int = 512
     align_corners: bool = False
     bn_eps: float = 1e-5
+    # model.test_cfg (encoder_decoder.py:155-201, 241-247) and the images the test pipeline's MultiScaleFlipAug hands to
+    # forward_test (test_time_aug.py:120-129): one (flip, flip_direction) pair per image, in its order
+    test_mode: str = "whole"
+    crop_size: Optional[Tuple[int, int]] = None
+    stride: Optional[Tuple[int, int]] = None
+    augs: Tuple[Tuple[bool, str], ...] = ((False, "horizontal"),)
 
     @property
     def feat_channels(self) -> int:
         return self.base_channels * 8 * 4
+
+    @property
+    def plain_inference(self) -> bool:
+        """whole_inference of one unflipped image: what ``peanut_pred_forward`` computes by itself."""
+        return self.test_mode == "whole" and len(self.augs) == 1 and not self.augs[0][0]
+
+    @property
+    def flip_codes(self) -> Tuple[int, ...]:
+        """``peanut_pred_infer_t.flip`` of ``augs``: 0 none, 1 horizontal, 2 vertical."""
+        return tuple(({"horizontal": 1, "vertical": 2}[d] if f else 0) for f, d in self.augs)
+
+
+_TEST_TRANSFORMS = ("Resize", "RandomFlip", "ImageToTensor", "Collect")
+
+
+def _pair(v, what: str) -> Tuple[int, int]:
+    if not isinstance(v, (tuple, list)) or len(v) != 2 or not all(isinstance(t, int) and t >= 1 for t in v):
+        raise ValueError(f"test_cfg.{what} must be a pair of positive ints (h, w), got {v!r}")
+    return int(v[0]), int(v[1])
+
+
+def _test_time_augs(ns) -> Tuple[Tuple[bool, str], ...]:
+    """The (flip, flip_direction) of every image ``MultiScaleFlipAug.__call__`` builds (test_time_aug.py:120-129), from
+    ``data['test']['pipeline'][1]``; a file without that entry runs the stock pipeline (one unflipped image)."""
+    default = ((False, "horizontal"),)
+    data = ns.get("data")
+    if not isinstance(data, dict) or not isinstance(data.get("test"), dict) or "pipeline" not in data["test"]:
+        return default
+    pipeline = data["test"]["pipeline"]
+    if len(pipeline) < 2 or pipeline[1].get("type") != "MultiScaleFlipAug":
+        raise ValueError("data.test.pipeline[1] must be MultiScaleFlipAug (nav/agent/prediction.py:125-127 replaces entry 0 only)")
+    aug = pipeline[1]
+    if aug.get("img_scale") is not None:
+        raise ValueError(f"MultiScaleFlipAug.img_scale must be None (multi-scale testing is not supported), got {aug.get('img_scale')!r}")
+    ratios = aug.get("img_ratios")
+    ratios = ratios if isinstance(ratios, list) else [ratios]
+    if ratios != [1.0]:
+        raise ValueError(f"MultiScaleFlipAug.img_ratios must be [1.0] (multi-scale testing is not supported), got {aug.get('img_ratios')!r}")
+    transforms = aug.get("transforms") or []
+    for t in transforms:
+        if t.get("type") not in _TEST_TRANSFORMS:
+            raise ValueError(f"test transform {t.get('type')!r} is not supported (only {', '.join(_TEST_TRANSFORMS)})")
+        if t["type"] == "Resize" and not t.get("keep_ratio", True):
+            raise ValueError("test transform Resize must have keep_ratio=True")
+    flip = bool(aug.get("flip", False))
+    directions = aug.get("flip_direction", "horizontal")
+    directions = directions if isinstance(directions, list) else [directions]
+    for d in directions:
+        if d not in ("horizontal", "vertical"):
+            raise ValueError(f"flip_direction must be 'horizontal' or 'vertical', got {d!r}")
+    if flip and not any(t["type"] == "RandomFlip" for t in transforms):
+        raise ValueError("MultiScaleFlipAug(flip=True) without a RandomFlip among its transforms: the reference would un-flip "
+                         "outputs whose inputs were never flipped; add dict(type='RandomFlip') or set flip=False")
+    augs = tuple((f, d) for f in ([False, True] if flip else [False]) for d in directions)
+    if len(augs) > 4:
+        raise ValueError(f"{len(augs)} test-time augmentations; at most 4 are supported")
+    return augs
 
 
 def pred_cfg_from_file(path: str) -> PredCfg:
@@ -51,6 +114,9 @@ def pred_cfg_from_file(path: str) -> PredCfg:
 
     Mirrors ``Config.fromfile`` (``nav/agent/prediction.py:146``) for the keys
     the forward needs; the file is plain python assignments, so it is exec'd.
+    ``model.test_cfg`` (whole / slide with ``crop_size`` and ``stride``) and the flips of
+    ``data['test']['pipeline'][1]`` (``MultiScaleFlipAug``) are honoured; what cannot be is
+    refused with a ``ValueError`` (INTEGRATION.md).
     """
     ns: Dict[str, object] = {}
     with open(path, "r") as f:
@@ -63,10 +129,17 @@ def pred_cfg_from_file(path: str) -> PredCfg:
                          f"{model.get('type')}({bb.get('type')}, {dh.get('type')})")
     if bb.get("depth") != 50:
         raise ValueError(f"only depth=50 is supported, got {bb.get('depth')}")
-    mode = (model.get("test_cfg") or {}).get("mode", "whole")
-    if mode != "whole":
-        raise ValueError(f"only test_cfg.mode='whole' is supported, got {mode!r}")
+    test_cfg = model.get("test_cfg") or {}
+    mode = test_cfg.get("mode", "whole")
+    crop = stride = None
+    if mode == "slide":
+        if test_cfg.get("crop_size") is None or test_cfg.get("stride") is None:
+            raise ValueError("test_cfg.mode='slide' needs crop_size and stride (encoder_decoder.py:162-163)")
+        crop, stride = _pair(test_cfg["crop_size"], "crop_size"), _pair(test_cfg["stride"], "stride")
+    elif mode != "whole":
+        raise ValueError(f"test_cfg.mode must be 'whole' or 'slide', got {mode!r}")
     return PredCfg(
+        test_mode=mode, crop_size=crop, stride=stride, augs=_test_time_augs(ns),
         in_channels=int(bb.get("in_channels", 3)),
         num_classes=int(dh["num_classes"]),
         strides=tuple(bb.get("strides", (1, 2, 2, 2))),
