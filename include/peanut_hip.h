@@ -879,6 +879,68 @@ int peanut_mapseq_inputs(const peanut_mapseq_t* seq, const peanut_mapseq_sample_
  * outside 1..C - 4. */
 int peanut_mapseq_bce(const peanut_mapseq_t* seq, const peanut_mapseq_sample_t* samples, int B, int S, const float* logits, int K,
                       double* sum_out);
+/* Augmented training batches (ABI 25): what the reference's train_pipeline (nav/pred_model_cfg.py:47-56: LoadMapFromFile, Resize
+ * at ratio 1, Pad, RandomCrop, RandomFlip, RandomRotate) makes of a sample, input and target, from sequences that stay on the
+ * device.  One sample (HOST struct, copied by value): its own sequence maps uint8 [T, C, W, H] (a batch draws from different
+ * files; C, W, H are shared), the snapshot t_idx, the crop offsets (off_r, off_c) into the padded map, flip (0 none, 1
+ * horizontal = the last axis, 2 vertical = the first map axis), rotate (0 off, else on) and the cosine and sine of the angle,
+ * formed by the caller in double. */
+typedef struct {
+  const uint8_t* maps;
+  int32_t T, t_idx, off_r, off_c, flip, rotate;
+  double cos_t, sin_t;
+} peanut_mapseq_aug_t;
+/* The batch: `size` = sizeof(peanut_mapseq_train_t) first; the map is padded with zeros at the bottom and right to
+ * (pad_r, pad_c), cropped to (S_r, S_c) at the sample's offsets, flipped, rotated about the centre of the crop.  Per sample and
+ * output cell (y, x) of the crop, with cy = (S_r - 1) / 2, cx = (S_c - 1) / 2:
+ *   rotation on:  ys = c (y - cy) - s (x - cx) + cy,  xs = s (y - cy) + c (x - cx) + cx   in double
+ *                 (mmcv.imrotate with center None and auto_bound False: cv2.getRotationMatrix2D(center, -angle, 1) and
+ *                 warpAffine without WARP_INVERSE_MAP)
+ *   tap(yi, xi):  0 outside [0, S_r) x [0, S_c) (the constant border; it takes part in the interpolation); else the flip is
+ *                 undone (xi <- S_c - 1 - xi for flip 1, yi <- S_r - 1 - yi for flip 2), r = yi + off_r, q = xi + off_c, and the
+ *                 tap is 0 where r >= W or q >= H (the padding), else the source cell (r, q)
+ *   img  fp32 [B, C, S_r, S_c]: rotation on: the bilinear blend of float(byte) / 255.0f at the taps (floor ys, floor xs),
+ *        (., +1), (+1, .), (+1, +1) of snapshot t_idx, the weights (1-fy)(1-fx), (1-fy) fx, fy (1-fx), fy fx formed in double and
+ *        rounded to fp32, summed in fp32 in that order; rotation off: float(byte) / 255.0f of tap(y, x), the bits of
+ *        peanut_mapseq_inputs
+ *   gt   uint8 [B, K, S_r, S_c] (may be NULL: not written): at the nearest tap (floor(ys + 0.5), floor(xs + 0.5)), or (y, x)
+ *        with rotation off: maps[T-1, 4+k, r, q] where maps[t_idx, 1, r, q] == 0, else 0 (train_prediction_model.py:85-89; the
+ *        explored mask is read at the source cell: the reference masks before it augments).
+ * Unpinned (cv2 is absent where the fixtures are made): cv2 quantises warpAffine's source coordinates to 1/1024 px and the
+ * bilinear fraction to 1/32 px; the rule here is exact in double and held to a float64 restatement and to scipy's
+ * affine_transform(mode='grid-constant').  Resize at ratio 1, Pad, RandomCrop, RandomFlip and the order of the random draws are
+ * pinned by the reference's own code.
+ * ONE launch for the batch on `stream`: a workgroup owns a 16 x 64 tile of a sample's crop, a thread four consecutive cells of a
+ * row.  Every element of img and gt is written.  No synchronisation, no allocation.  PEANUT_EINVAL with nothing enqueued: a wrong
+ * size, a null pointer (gt excepted), B outside 1..PEANUT_MAPSEQ_MAX_SAMPLES, C < 5, K outside 1..C - 4, a pad smaller than the
+ * map, a crop larger than the pad, an offset outside [0, pad - S], a t_idx outside [0, T), flip outside 0..2, a non-finite cos_t /
+ * sin_t or cos_t^2 + sin_t^2 not within 1e-9 of 1. */
+typedef struct {
+  uint64_t size;                          /* sizeof(peanut_mapseq_train_t) */
+  int32_t B, C, W, H;
+  int32_t pad_r, pad_c, S_r, S_c;
+  int32_t K, reserved;
+  const peanut_mapseq_aug_t* samples;     /* HOST [B] */
+  float* img;                             /* device [B, C, S_r, S_c] */
+  uint8_t* gt;                            /* device [B, K, S_r, S_c], or NULL */
+  void* stream;
+} peanut_mapseq_train_t;
+int peanut_mapseq_train_batch(const peanut_mapseq_train_t* batch);
+/* The loss of peanut_mapseq_bce against a GIVEN target (the gt of peanut_mapseq_train_batch): logits device fp32
+ * [B, K, S_r, S_c], gt device uint8 of that shape, y = float(byte) / 255.0f; the same cell formula, the same partition (chunks
+ * of 1024 cells of the row-major window) and the same fixed order, so that a target equal to the one peanut_mapseq_bce derives
+ * gives its bits.  sum_out: HOST double [B][K].  `size` = sizeof(peanut_mapseq_bce_dense_t) first.  Synchronises `stream` (the
+ * sums come back to the host).  PEANUT_EINVAL with nothing enqueued: a wrong size, a null pointer, B outside
+ * 1..PEANUT_MAPSEQ_MAX_SAMPLES, K, S_r or S_c below 1, a window of 2^31 cells or more. */
+typedef struct {
+  uint64_t size;                          /* sizeof(peanut_mapseq_bce_dense_t) */
+  int32_t B, K, S_r, S_c;
+  const float* logits;
+  const uint8_t* gt;
+  double* sum_out;                        /* HOST [B][K] */
+  void* stream;
+} peanut_mapseq_bce_dense_t;
+int peanut_mapseq_bce_dense(const peanut_mapseq_bce_dense_t* batch);
 
 /* ------------------------------------------------------------------------------------------
  * The agent's visualisation frame (ABI 23; csrc/vis.hip): what Agent_Helper._visualize (nav/agent/agent_helper.py:496-621) builds on

@@ -17,7 +17,7 @@ from . import build as _build
 
 _LOCK = threading.Lock()
 _LIB = None
-ABI_VERSION = 24   # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
+ABI_VERSION = 25   # must equal peanut_abi_version() of the loaded library (struct layouts, argument lists)
 
 
 class PeanutHipError(RuntimeError):
@@ -100,6 +100,25 @@ class MapSeqEncodeC(C.Structure):
 class MapSeqSampleC(C.Structure):
     """peanut_mapseq_sample_t: snapshot index and first cell of one sample's window (12 bytes)."""
     _fields_ = [("t_idx", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32)]
+
+
+class MapSeqAugC(C.Structure):
+    """peanut_mapseq_aug_t: one sample of peanut_mapseq_train_batch: its sequence, snapshot, crop offsets, flip, rotation (48 bytes)."""
+    _fields_ = [("maps", C.c_void_p), ("T", C.c_int32), ("t_idx", C.c_int32), ("off_r", C.c_int32), ("off_c", C.c_int32),
+                ("flip", C.c_int32), ("rotate", C.c_int32), ("cos_t", C.c_double), ("sin_t", C.c_double)]
+
+
+class MapSeqTrainC(C.Structure):
+    """peanut_mapseq_train_t: the descriptor of peanut_mapseq_train_batch (``size`` first; ``samples`` a host array of B entries)."""
+    _fields_ = [("size", C.c_uint64), ("B", C.c_int32), ("C", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
+                ("pad_r", C.c_int32), ("pad_c", C.c_int32), ("S_r", C.c_int32), ("S_c", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32),
+                ("samples", C.POINTER(MapSeqAugC)), ("img", C.c_void_p), ("gt", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class MapSeqBceDenseC(C.Structure):
+    """peanut_mapseq_bce_dense_t: the descriptor of peanut_mapseq_bce_dense (``size`` first; ``sum_out`` a host array [B][K])."""
+    _fields_ = [("size", C.c_uint64), ("B", C.c_int32), ("K", C.c_int32), ("S_r", C.c_int32), ("S_c", C.c_int32),
+                ("logits", C.c_void_p), ("gt", C.c_void_p), ("sum_out", C.POINTER(C.c_double)), ("stream", C.c_void_p)]
 
 
 PLAN_LINE_POINTS = 26      # PEANUT_PLAN_LINE_POINTS
@@ -268,6 +287,8 @@ SIGNATURES = {
     "peanut_mapseq_encode": (C.c_int, [C.POINTER(MapSeqEncodeC)]),
     "peanut_mapseq_inputs": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P]),
     "peanut_mapseq_bce": (C.c_int, [C.POINTER(MapSeqC), C.POINTER(MapSeqSampleC), C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_double)]),
+    "peanut_mapseq_train_batch": (C.c_int, [C.POINTER(MapSeqTrainC)]),
+    "peanut_mapseq_bce_dense": (C.c_int, [C.POINTER(MapSeqBceDenseC)]),
     "peanut_comm_unique_id": (C.c_int, [C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_ubyte * 128)]),
     "peanut_comm_destroy": (None, [_P]),

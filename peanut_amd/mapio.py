@@ -7,7 +7,9 @@ PEANUT map datasets drive the benchmark / parity runs.
 For HIP tensors the sequence lives on the device (csrc/mapio.hip, ABI 21): ``MapSequenceRecorder`` records the snapshots of
 lock-step episodes as an ``on_step`` hook of ``replay.run_episode`` / ``run_episodes``, ``model_input_batch`` and ``bce_score``
 make the model inputs and the reference's loss from an uploaded uint8 sequence, and ``evaluate`` scores a checkpoint on the
-files of a dataset.  The host functions below are what they are held against."""
+files of a dataset.  The host functions below are what they are held against.  ABI 25 adds the training side: ``MapStore`` keeps a
+dataset on the device, ``TrainAugment`` draws the reference's augmentation parameters, ``train_batch`` / ``TrainBatcher`` build
+augmented batches, input and target, in one launch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -328,24 +330,298 @@ def dataset_samples(paths, t_indices: Iterable[int] = range(10)) -> List[tuple]:
     return [(f, t) for f in dataset_files(paths) for t in ts]
 
 
-def evaluate(model, paths, t_indices: Iterable[int] = range(10), window: Optional[int] = None, batch: Optional[int] = None) -> Dict:
+# ---- augmented training batches (peanut_mapseq_train_batch, ABI 25) ----------------------------------------------------------
+PARAMS_DTYPE = np.dtype([("off_r", np.int32), ("off_c", np.int32), ("flip", np.int32), ("rotate", np.int32), ("angle", np.float64)])
+FLIP_CODES = {"horizontal": 1, "vertical": 2}     # horizontal = the last axis, vertical = the first map axis (mmcv.imflip on [W,H,C])
+
+
+def _pair(v, what):
+    v = (int(v), int(v)) if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)
+    if len(v) != 2 or min(v) < 1:
+        raise ValueError(f"{what} must be a positive size (rows, columns), got {v}")
+    return v
+
+
+class TrainAugment:
+    """The random part of the reference's ``train_pipeline`` (nav/pred_model_cfg.py:47-56) -- ``Resize`` at ratio 1, ``Pad``,
+    ``RandomCrop``, ``RandomFlip``, ``RandomRotate`` -- as parameter rows for ``train_batch``.  Owns a ``np.random.RandomState(seed)``
+    and draws from it, per sample and in the reference's order (mmseg/datasets/pipelines/transforms.py:205, 603-604, 359, 706-707):
+    ``random_sample()`` (Resize; consumed), ``randint(0, margin_r + 1)``, ``randint(0, margin_c + 1)``, ``rand()`` (flip),
+    ``rand()`` and ``uniform(lo, hi)`` (rotation: both always drawn).  Under ``np.random.seed(seed)`` the reference's pipeline makes
+    the same draws bit for bit."""
+
+    def __init__(self, pad, crop, flip_prob=0.5, flip_direction="horizontal", rotate_prob=1.0, degree=180, seed=0):
+        self.pad, self.crop = _pair(pad, "pad"), _pair(crop, "crop")
+        if self.crop[0] > self.pad[0] or self.crop[1] > self.pad[1]:
+            raise ValueError(f"the crop {self.crop} is larger than the pad {self.pad}")
+        if flip_direction not in FLIP_CODES:
+            raise ValueError(f"flip_direction must be 'horizontal' or 'vertical', got {flip_direction!r}")
+        if not (0.0 <= float(flip_prob) <= 1.0 and 0.0 <= float(rotate_prob) <= 1.0):
+            raise ValueError("probabilities must lie in [0, 1]")
+        if isinstance(degree, (int, float)):
+            if degree <= 0:
+                raise ValueError(f"degree {degree} should be positive")
+            degree = (-degree, degree)
+        if len(degree) != 2:
+            raise ValueError(f"degree {degree} should be a number or (min, max)")
+        self.flip_prob, self.flip_code, self.flip_direction = float(flip_prob), FLIP_CODES[flip_direction], flip_direction
+        self.rotate_prob, self.degree = float(rotate_prob), (min(*degree), max(*degree))
+        self.seed = seed
+        self.rng = np.random.RandomState(seed)
+
+    @classmethod
+    def identity(cls, map_shape, seed=0):
+        """pad = crop = the map, no flip, no rotation: the batch is ``model_input_batch`` and the target of :85-89."""
+        return cls(map_shape, map_shape, flip_prob=0.0, rotate_prob=0.0, seed=seed)
+
+    @classmethod
+    def from_pipeline(cls, cfg_list, seed=0):
+        """From a ``train_pipeline`` list.  Exactly the reference's sequence is built: LoadMapFromFile, Resize, Pad, RandomCrop,
+        RandomFlip, RandomRotate, then formatting (DefaultFormatBundle, Collect).  ``ValueError`` for what is not: a Resize
+        ``ratio_range`` other than (1, 1) or an ``img_scale``, ``cat_max_ratio < 1``, ``size_divisor``, non-zero pad values, a
+        RandomRotate ``center`` or ``auto_bound``, any other transform, another order."""
+        want = ["Resize", "Pad", "RandomCrop", "RandomFlip", "RandomRotate"]
+        got, kw = [], {}
+        for cfg in cfg_list:
+            cfg = dict(cfg)
+            typ = cfg.pop("type", None)
+            if typ in ("LoadMapFromFile", "DefaultFormatBundle", "Collect"):
+                continue
+            if typ not in want:
+                raise ValueError(f"transform {typ!r} is not built")
+            got.append(typ)
+            if typ == "Resize":
+                if cfg.get("img_scale") is not None:
+                    raise ValueError("Resize with an img_scale is not built")
+                rr = cfg.get("ratio_range")
+                if rr is None or tuple(float(r) for r in rr) != (1.0, 1.0):
+                    raise ValueError(f"Resize ratio_range {rr} is not built: only (1, 1)")
+                if not cfg.get("keep_ratio", True) or cfg.get("min_size") is not None:
+                    raise ValueError("Resize with keep_ratio=False or a min_size is not built")
+            elif typ == "Pad":
+                if cfg.get("size_divisor") is not None or cfg.get("size") is None:
+                    raise ValueError("Pad needs a fixed size; size_divisor is not built")
+                if cfg.get("pad_val", 0) != 0 or cfg.get("seg_pad_val", 255) != 0:
+                    raise ValueError("Pad with non-zero pad values is not built (pad_val and seg_pad_val must be 0)")
+                kw["pad"] = cfg["size"]
+            elif typ == "RandomCrop":
+                if cfg.get("cat_max_ratio", 1.0) < 1.0:
+                    raise ValueError("RandomCrop with cat_max_ratio < 1 is not built")
+                kw["crop"] = cfg["crop_size"]
+            elif typ == "RandomFlip":
+                prob = cfg.get("prob", cfg.get("flip_ratio"))       # (mmcv renames flip_ratio to prob)
+                if prob is None:
+                    raise ValueError("RandomFlip needs a prob")
+                kw["flip_prob"], kw["flip_direction"] = prob, cfg.get("direction", "horizontal")
+            else:
+                if cfg.get("center") is not None or cfg.get("auto_bound", False):
+                    raise ValueError("RandomRotate with a center or auto_bound is not built")
+                if cfg.get("pad_val", 0) != 0 or cfg.get("seg_pad_val", 255) != 0:
+                    raise ValueError("RandomRotate with non-zero pad values is not built (pad_val and seg_pad_val must be 0)")
+                kw["rotate_prob"], kw["degree"] = cfg["prob"], cfg["degree"]
+        if got != want:
+            raise ValueError(f"the pipeline's transforms are {got}; built is exactly {want}")
+        return cls(seed=seed, **kw)
+
+    def draw(self, n, map_shape):
+        """The parameter rows of ``n`` samples of ``map_shape`` = (W, H) maps: a ``PARAMS_DTYPE`` array (off_r, off_c, flip code,
+        rotate 0 / 1, angle in degrees).  The angle is drawn, and kept, also where ``rotate`` is 0."""
+        W, H = (int(v) for v in map_shape)
+        if self.pad[0] < W or self.pad[1] < H:
+            raise ValueError(f"the pad {self.pad} is smaller than the {W} x {H} map")         # (mmcv.impad asserts)
+        rows = np.zeros(int(n), PARAMS_DTYPE)
+        rng = self.rng
+        for row in rows:
+            rng.random_sample()                                                         # Resize: ratio_range (1, 1)
+            row["off_r"] = rng.randint(0, self.pad[0] - self.crop[0] + 1)
+            row["off_c"] = rng.randint(0, self.pad[1] - self.crop[1] + 1)
+            row["flip"] = self.flip_code if rng.rand() < self.flip_prob else 0
+            row["rotate"] = 1 if rng.rand() < self.rotate_prob else 0
+            row["angle"] = rng.uniform(self.degree[0], self.degree[1])
+        return rows
+
+
+def rotation_terms(angle_deg):
+    """(cos, sin) of an angle in degrees as ``train_batch`` hands them to the kernel (and tests/train_batch_cases.py restates)."""
+    import math
+    a = math.radians(float(angle_deg))
+    return math.cos(a), math.sin(a)
+
+
+def train_batch(seqs, t_idx, params, pad, crop, K=6, img=None, gt=None):
+    """A training batch, input and target, by the reference's pipeline in one launch per 64 samples (``peanut_mapseq_train_batch``).
+    ``seqs``: one uint8 [T,C,W,H] device tensor for all samples, or one per sample (of one C, W, H; T may differ); ``t_idx``: the
+    snapshot per sample; ``params``: ``PARAMS_DTYPE`` rows (``TrainAugment.draw``); ``pad`` / ``crop``: (rows, columns).  Returns
+    ``(img, gt)``: float32 [B,C,S_r,S_c] and uint8 [B,K,S_r,S_c] on the device, every element written; the target is the last
+    snapshot's channels ``4:4+K`` where channel 1 of snapshot ``t_idx`` is unexplored.  Enqueued on the current stream."""
+    from . import _lib
+    ts = [int(t) for t in t_idx] if isinstance(t_idx, Iterable) else [int(t_idx)]
+    B = len(ts)
+    seqs = [seqs] * B if isinstance(seqs, torch.Tensor) else list(seqs)
+    params = np.asarray(params)
+    if B < 1 or len(seqs) != B or params.dtype != PARAMS_DTYPE or params.shape != (B,):
+        raise ValueError("seqs, t_idx and params must name the same, positive number of samples (params: PARAMS_DTYPE rows)")
+    for m in seqs:
+        if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.uint8 and m.dim() == 4 and m.is_contiguous()):
+            raise ValueError("every sequence must be a contiguous uint8 [T,C,W,H] tensor on the HIP device (mapio.to_device)")
+    dev, (Cn, W, H) = seqs[0].device, tuple(seqs[0].shape[1:])
+    if any(m.device != dev or tuple(m.shape[1:]) != (Cn, W, H) for m in seqs):
+        raise ValueError("the sequences of one batch must share C, W, H and the device")
+    pad, crop = _pair(pad, "pad"), _pair(crop, "crop")
+    K = int(K)
+    if img is None:
+        img = torch.empty((B, Cn) + crop, dtype=torch.float32, device=dev)
+    elif img.dtype != torch.float32 or tuple(img.shape) != (B, Cn) + crop or not img.is_contiguous() or img.device != dev:
+        raise ValueError("img must be a contiguous float32 [B,C,S_r,S_c] tensor on the sequences' device")
+    if gt is None:
+        gt = torch.empty((B, max(K, 0)) + crop, dtype=torch.uint8, device=dev)
+    elif gt.dtype != torch.uint8 or tuple(gt.shape) != (B, K) + crop or not gt.is_contiguous() or gt.device != dev:
+        raise ValueError("gt must be a contiguous uint8 [B,K,S_r,S_c] tensor on the sequences' device")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        for lo in range(0, B, _lib.MAPSEQ_MAX_SAMPLES):
+            hi = min(B, lo + _lib.MAPSEQ_MAX_SAMPLES)
+            arr = (_lib.MapSeqAugC * (hi - lo))()
+            for k in range(lo, hi):
+                a, p = arr[k - lo], params[k]
+                a.maps, a.T, a.t_idx = seqs[k].data_ptr(), seqs[k].shape[0], ts[k]
+                a.off_r, a.off_c, a.flip, a.rotate = int(p["off_r"]), int(p["off_c"]), int(p["flip"]), int(p["rotate"])
+                a.cos_t, a.sin_t = rotation_terms(p["angle"])
+            d = _lib.MapSeqTrainC(C.sizeof(_lib.MapSeqTrainC), hi - lo, Cn, W, H, pad[0], pad[1], crop[0], crop[1], K, 0, arr,
+                                  img[lo:hi].data_ptr(), gt[lo:hi].data_ptr(), _lib.current_stream_ptr(dev))
+            _lib.check(lib.peanut_mapseq_train_batch(C.byref(d)), "peanut_mapseq_train_batch")
+    return img, gt
+
+
+def bce_score_target(logits: torch.Tensor, gt: torch.Tensor) -> np.ndarray:
+    """``bce_score`` against a given uint8 target [B,K,S_r,S_c] (the ``gt`` of ``train_batch``): the same loss, partition and order
+    (``peanut_mapseq_bce_dense``), so the identity augmentation gives ``bce_score``'s bits.  Returns float64 [B,K] on the host
+    (synchronises)."""
+    from . import _lib
+    if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4):
+        raise ValueError("logits must be a float32 [B,K,S_r,S_c] tensor on the HIP device")
+    if not (isinstance(gt, torch.Tensor) and gt.dtype == torch.uint8 and gt.device == logits.device and tuple(gt.shape) == tuple(logits.shape)):
+        raise ValueError(f"gt must be a uint8 tensor of the logits' shape {tuple(logits.shape)} and device")
+    logits, gt = logits.contiguous(), gt.contiguous()
+    B, K, Sr, Sc = logits.shape
+    out = np.empty((B, K), np.float64)
+    lib, dev = _lib.load(), logits.device
+    with torch.cuda.device(dev):
+        for lo in range(0, B, _lib.MAPSEQ_MAX_SAMPLES):
+            hi = min(B, lo + _lib.MAPSEQ_MAX_SAMPLES)
+            part = np.empty((hi - lo, K), np.float64)
+            d = _lib.MapSeqBceDenseC(C.sizeof(_lib.MapSeqBceDenseC), hi - lo, K, Sr, Sc, logits[lo:hi].data_ptr(), gt[lo:hi].data_ptr(),
+                                     part.ctypes.data_as(C.POINTER(C.c_double)), _lib.current_stream_ptr(dev))
+            _lib.check(lib.peanut_mapseq_bce_dense(C.byref(d)), "peanut_mapseq_bce_dense")
+            out[lo:hi] = part
+    return out
+
+
+def compact_sequence(maps: np.ndarray, t_indices: Iterable[int] = range(10)) -> np.ndarray:
+    """What training reads of a stored sequence: the snapshots ``t_indices`` (in that order) followed by the last one, so that
+    ``maps[-1]`` stays the target's source and sample ``t_indices[i]`` is snapshot ``i``.  A 20-snapshot file shrinks to 11."""
+    ts = [int(t) for t in t_indices]
+    if maps.ndim != 4 or any(not 0 <= t < maps.shape[0] for t in ts):
+        raise ValueError(f"t_indices {ts} outside the sequence {maps.shape}")
+    return np.ascontiguousarray(maps[ts + [maps.shape[0] - 1]])
+
+
+class MapStore:
+    """A dataset in device memory as the bytes it is stored in: every file of ``dataset_files(paths)`` is loaded once, compacted
+    (``compact_sequence``) and uploaded.  ``samples``: ``[(file, t_idx)]`` in ``dataset_samples`` order; ``sample(i)`` gives the
+    device sequence and the snapshot index within it.  Raises ``ValueError`` when the dataset exceeds ``max_bytes``."""
+
+    def __init__(self, paths, device="cuda:0", t_indices: Iterable[int] = range(10), max_bytes: Optional[int] = None):
+        self.t_indices = [int(t) for t in t_indices]
+        self.files = dataset_files(paths)
+        if not self.files:
+            raise ValueError("no map files")
+        self.device = torch.device(device)
+        self.seqs: List[torch.Tensor] = []
+        self.nbytes = 0
+        for f in self.files:
+            seq = compact_sequence(load_map_sequence(f), self.t_indices)
+            if self.seqs and tuple(seq.shape[1:]) != tuple(self.seqs[0].shape[1:]):
+                raise ValueError(f"{f}: maps of {seq.shape[1:]}, the dataset's are {tuple(self.seqs[0].shape[1:])}")
+            self.nbytes += seq.nbytes
+            if max_bytes is not None and self.nbytes > max_bytes:
+                raise ValueError(f"the dataset exceeds max_bytes = {max_bytes} at {f} ({self.nbytes} bytes so far)")
+            self.seqs.append(to_device(seq, self.device))
+        self.samples = [(f, t) for f in self.files for t in self.t_indices]
+        self.map_shape = tuple(self.seqs[0].shape[2:])
+        self.channels = int(self.seqs[0].shape[1])
+
+    def __len__(self):
+        return len(self.samples)
+
+    def sample(self, i):
+        n = len(self.t_indices)
+        return self.seqs[i // n], i % n
+
+
+class TrainBatcher:
+    """Batches of a ``MapStore`` under a ``TrainAugment``: iterating it walks ONE epoch of a seeded permutation of the samples
+    (``np.random.RandomState(seed)``, a new permutation per epoch; the last batch of an epoch may be short), and every batch is
+    ``{'img': float32 [B,C,S_r,S_c], 'gt_semantic_seg': uint8 [B,K,S_r,S_c], 'params': rows}`` on the device, one launch.
+    ``batch_of(indices)`` builds the batch of the given samples (it draws their parameters)."""
+
+    def __init__(self, store: MapStore, augment: TrainAugment, batch: int = 8, seed=0, K: int = 6):
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        self.store, self.augment, self.batch, self.K = store, augment, int(batch), int(K)
+        self.rng = np.random.RandomState(seed)
+        self.epoch = 0
+
+    def __len__(self):
+        return (len(self.store) + self.batch - 1) // self.batch
+
+    def batch_of(self, indices) -> Dict:
+        picks = [self.store.sample(int(i)) for i in indices]
+        params = self.augment.draw(len(picks), self.store.map_shape)
+        img, gt = train_batch([s for s, _ in picks], [t for _, t in picks], params, self.augment.pad, self.augment.crop, K=self.K)
+        return {"img": img, "gt_semantic_seg": gt, "params": params}
+
+    def __iter__(self):
+        order = self.rng.permutation(len(self.store))
+        self.epoch += 1
+        for lo in range(0, len(order), self.batch):
+            yield self.batch_of(order[lo:lo + self.batch])
+
+
+def evaluate(model, paths, t_indices: Iterable[int] = range(10), window: Optional[int] = None, batch: Optional[int] = None,
+             augment: Optional[TrainAugment] = None) -> Dict:
     """Score a prediction model on stored map sequences with the loss it was trained on.  Per file (``dataset_files``): upload the
     uint8 sequence once, build the inputs of its ``t_indices`` on the device, run ``model.get_prediction_batch(...,
     apply_sigmoid=False)`` in batches of ``batch`` (default: all samples of a file), score with ``bce_score``.  ``model``: a
     ``PEANUT_Prediction_Model``.  Returns ``loss`` (the mean over all cells: ``reduction='mean'``, weight 1.0),
-    ``loss_per_channel`` [K] and ``n_maps``."""
+    ``loss_per_channel`` [K] and ``n_maps``.
+
+    ``augment``: a ``TrainAugment``: the loss under the training augmentation instead (how robust a checkpoint is to the shifts,
+    flips and rotations it was trained with).  Files and batches are walked in the same order; per batch the route is
+    ``TrainBatcher.batch_of`` -> forward -> ``bce_score_target``, the window is the augmentation's crop (``window`` must be None), and
+    the identity augmentation returns what the plain call returns."""
     ts = [int(t) for t in t_indices]
     seg = getattr(model, "model", model)
     device = seg.device
     total, cells, n_maps = None, 0, 0
+    if augment is not None and window is not None:
+        raise ValueError("with an augmentation the window is its crop: give no window")
     for f in dataset_files(paths):
-        maps_dev = to_device(load_map_sequence(f), device)
         step = len(ts) if not batch else int(batch)
+        if augment is not None:
+            batcher = TrainBatcher(MapStore([f], device, ts), augment, batch=step, K=seg.cfg.num_classes)
+        else:
+            maps_dev = to_device(load_map_sequence(f), device)
         for lo in range(0, len(ts), step):
             part = ts[lo:lo + step]
-            x = model_input_batch(maps_dev, part, window)
-            logits = seg.check_range(model.get_prediction_batch(x, apply_sigmoid=False))
-            sums = bce_score(logits, maps_dev, part, window)
+            if augment is not None:
+                b = batcher.batch_of(range(lo, lo + len(part)))
+                logits = seg.check_range(model.get_prediction_batch(b["img"], apply_sigmoid=False))
+                sums = bce_score_target(logits, b["gt_semantic_seg"])
+            else:
+                x = model_input_batch(maps_dev, part, window)
+                logits = seg.check_range(model.get_prediction_batch(x, apply_sigmoid=False))
+                sums = bce_score(logits, maps_dev, part, window)
             total = sums.sum(axis=0) if total is None else total + sums.sum(axis=0)
             cells += len(part) * logits.shape[2] * logits.shape[3]
             n_maps += len(part)

@@ -17,7 +17,14 @@ medians with [min, max] over ``--repeats`` windows; every shape is warmed up; ho
     ``forward_alone``    the forward of a file's ten samples on inputs already on the device;
     ``load_alone``       `np.load` of the files (both routes contain it).
 
-    python tools/bench_mapio.py [--out profiles/mapio] [--repeats 5] [--snapshot-only | --evaluate-only]
+* ``train_batch``  (``--train-batch`` -> <out>/train_batch.jsonl) the workload's own shape: 960 x 960 x 14 maps, pad 1200, crop
+  960, B = 8, K = 6, samples from two compacted sequences [11, 14, 960, 960] on the device:
+    ``train_off`` / ``train_on``  one `peanut_mapseq_train_batch` with the rotation off / on (offsets, flips and angles as drawn);
+    ``model_input_batch``         the ABI 21 call at the same B and S: the same fp32 bytes, no gather, no target;
+    ``host_sample``               the pipeline restated per sample with NumPy and scipy (pad, crop, flip, `affine_transform`), on a
+                                  sequence already in memory; ``load_file`` is `np.load` of a [20, 14, 960, 960] file, timed apart.
+
+    python tools/bench_mapio.py [--out profiles/mapio] [--repeats 5] [--snapshot-only | --evaluate-only | --train-batch]
 """
 import argparse
 import json
@@ -186,18 +193,106 @@ def evaluate(dev, repeats, n_files=2, window=720):
     return [rec]
 
 
+def host_sample(maps, t, p, pad, crop, K):
+    """The reference's pipeline on one sample, restated with NumPy and scipy: fp32 image, uint8 target."""
+    import math
+
+    from scipy.ndimage import affine_transform
+    W, H = maps.shape[2:]
+    img = maps[t].astype(np.float32) / np.float32(255.)
+    gt = maps[-1, 4:4 + K] * (maps[t, 1] == 0)
+    out = []
+    for a, order in ((img, 1), (gt, 0)):
+        a = np.pad(a, [(0, 0), (0, pad[0] - W), (0, pad[1] - H)])[:, p["off_r"]:p["off_r"] + crop[0], p["off_c"]:p["off_c"] + crop[1]]
+        a = a[:, :, ::-1] if p["flip"] == 1 else a[:, ::-1] if p["flip"] == 2 else a
+        if p["rotate"]:
+            c, s = math.cos(math.radians(p["angle"])), math.sin(math.radians(p["angle"]))
+            cy, cx = (crop[0] - 1) / 2.0, (crop[1] - 1) / 2.0
+            off = [cy - c * cy + s * cx, cx - s * cy - c * cx]
+            a = np.stack([affine_transform(np.ascontiguousarray(pl), [[c, -s], [s, c]], offset=off, order=order, mode="grid-constant", cval=0)
+                          for pl in a])
+        out.append(np.ascontiguousarray(a))
+    return out
+
+
+def train_batch(dev, repeats, B=8, calls=100):
+    from peanut_amd import mapio
+    pad, crop, K, W = (1200, 1200), (960, 960), 6, 960
+    full = [np.stack([(synth_map(100 * f + min(t, 3)) * 255).astype(np.uint8) for t in range(4)])[[min(t, 3) for t in range(20)]] for f in range(2)]
+    tmp = tempfile.mkdtemp(prefix="bench_mapio_")
+    path = os.path.join(tmp, "f00000.npz")
+    np.savez_compressed(path, maps=full[0])
+    seqs = [mapio.to_device(mapio.compact_sequence(m), dev) for m in full]
+    ts = [b % 10 for b in range(B)]
+    rows = mapio.TrainAugment(pad, crop, seed=0).draw(B, (W, W))          # the reference's settings: flip 0.5, rotation always
+    rows_off = rows.copy()
+    rows_off["rotate"] = 0
+    img = torch.empty((B, 14) + crop, dtype=torch.float32, device=dev)
+    gt = torch.empty((B, K) + crop, dtype=torch.uint8, device=dev)
+    batch_seqs = [seqs[b % 2] for b in range(B)]
+    host_maps = mapio.compact_sequence(full[0])
+
+    def train_off(n):
+        for _ in range(n):
+            mapio.train_batch(batch_seqs, ts, rows_off, pad, crop, K=K, img=img, gt=gt)
+
+    def train_on(n):
+        for _ in range(n):
+            mapio.train_batch(batch_seqs, ts, rows, pad, crop, K=K, img=img, gt=gt)
+
+    def inputs(n):
+        for _ in range(n):
+            mapio.model_input_batch(seqs[0], ts, window=W, out=img)
+
+    def host(n):
+        for i in range(n):
+            host_sample(host_maps, ts[i % B], rows[i % B], pad, crop, K)
+
+    def load(n):
+        for _ in range(n):
+            mapio.load_map_sequence(path)
+    sides = [("train_off", train_off, calls), ("train_on", train_on, calls), ("model_input_batch", inputs, calls), ("host_sample", host, 1),
+             ("load_file", load, 1)]
+    for name, fn, n in sides:
+        fn(min(n, 3))
+    torch.cuda.synchronize()
+    t = {name: [] for name, _, _n in sides}
+    for _ in range(repeats):
+        for name, fn, n in sides:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(n)
+            torch.cuda.synchronize()
+            t[name].append((time.perf_counter() - t0) / n * 1e3)
+    sp = {name: spread(v) for name, v in t.items()}
+    cells = B * crop[0] * crop[1]
+    written = {"train_off": cells * (14 * 4 + K), "train_on": cells * (14 * 4 + K), "model_input_batch": cells * 14 * 4}
+    rec = {"section": "train_batch", "B": B, "map": [14, W, W], "pad": list(pad), "crop": list(crop), "K": K, "calls_per_window": {n: c for n, _, c in sides},
+           "ms": sp, "bytes_written_per_call": written,
+           "written_GBps": {n: round(b / sp[n]["median"] / 1e6, 1) for n, b in written.items()},
+           "train_on_over_model_input_batch": round(sp["train_on"]["median"] / sp["model_input_batch"]["median"], 2),
+           "train_off_over_model_input_batch": round(sp["train_off"]["median"] / sp["model_input_batch"]["median"], 2),
+           "host_batch_over_train_on": round(B * sp["host_sample"]["median"] / sp["train_on"]["median"], 1)}
+    print(f"train_batch: {rec}", file=sys.stderr, flush=True)
+    os.remove(path)
+    os.rmdir(tmp)
+    return [rec]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mapio"))
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--snapshot-only", action="store_true")
     ap.add_argument("--evaluate-only", action="store_true")
+    ap.add_argument("--train-batch", action="store_true", help="only the train_batch section")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_mapio.py measures on the GPU; none is visible")
     dev = torch.device("cuda", torch.cuda.current_device())
     os.makedirs(a.out, exist_ok=True)
-    for name, fn, skip in (("snapshot", snapshot, a.evaluate_only), ("evaluate", evaluate, a.snapshot_only)):
+    for name, fn, skip in (("snapshot", snapshot, a.evaluate_only or a.train_batch), ("evaluate", evaluate, a.snapshot_only or a.train_batch),
+                           ("train_batch", train_batch, not a.train_batch)):
         if skip:
             continue
         with open(os.path.join(a.out, name + ".jsonl"), "w") as f:

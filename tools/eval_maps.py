@@ -5,8 +5,11 @@ sorted by name).  The sequences go up as uint8, inputs, forward and loss stay on
 
     python tools/eval_maps.py data/saved_maps/val_80 --weights nav/pred_model_wts.pth [--cfg nav/pred_model_cfg.py]
                               [--precision fp32|bf16x6|fp16x3|bf16x3] [--window 720] [--t-indices 0-9] [--batch 10]
+                              [--augment SEED [--pad 1200 --crop 960]]
 
 prints one JSON line: loss (mean over all cells, reduction='mean', weight 1.0), loss_per_channel, n_maps, maps_per_s.
+`--augment SEED` scores under the training augmentation instead (the reference's train_pipeline: pad, random crop, flip 0.5, rotation
++-180 degrees, drawn from SEED): how robust the checkpoint is to the shifts and rotations it was trained with.
 `--seeded SEED` replaces the checkpoint by the seeded synthetic weights (a dry run of the path, not a score)."""
 import argparse
 import json
@@ -41,6 +44,9 @@ def main():
     ap.add_argument("--window", type=int, default=None, help="centre crop fed to the model (default: the whole map)")
     ap.add_argument("--t-indices", default="0-9")
     ap.add_argument("--batch", type=int, default=None, help="samples per forward (default: all samples of a file)")
+    ap.add_argument("--augment", type=int, default=None, metavar="SEED", help="score under the training augmentation drawn from SEED")
+    ap.add_argument("--pad", type=int, default=1200, help="with --augment: the pad size (nav/pred_model_cfg.py:50)")
+    ap.add_argument("--crop", type=int, default=960, help="with --augment: the crop size (nav/pred_model_cfg.py:51)")
     ap.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args()
     if (a.weights is None) == (a.seeded is None):
@@ -58,10 +64,11 @@ def main():
     if not files:
         sys.exit("no .npz files under " + " ".join(a.paths))
     t0 = time.perf_counter()
-    res = mapio.evaluate(model, files, t_indices=_t_indices(a.t_indices), window=a.window, batch=a.batch)
+    augment = mapio.TrainAugment(a.pad, a.crop, seed=a.augment) if a.augment is not None else None
+    res = mapio.evaluate(model, files, t_indices=_t_indices(a.t_indices), window=a.window, batch=a.batch, augment=augment)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    res.update(precision=a.precision, files=len(files), window=a.window, seconds=round(dt, 3), maps_per_s=round(res["n_maps"] / dt, 2))
+    res.update(precision=a.precision, files=len(files), window=a.window, augment=a.augment, seconds=round(dt, 3), maps_per_s=round(res["n_maps"] / dt, 2))
     print(json.dumps(res))
 
 
